@@ -354,6 +354,39 @@ def cpu_baseline(device, sample_users=8):
                           '|loss| difference, max |pos/neg score| difference, worst max|dg|/max|g| over the adapter gradients')
 
 
+DUMP_MAX_ELEMS = 1 << 22            # --dump-outputs: float32 elements kept per array (16 MB); loss + 2 arrays stay under 64 MB in all
+
+
+def dump_positions(n, k):
+    """The fixed sample of --dump-outputs: k distinct positions of [0, n), sorted -- one per stratum [j n / k, (j + 1) n / k), drawn with seed
+    SEED (the same positions for every build; no permutation of all n positions is built)."""
+    j = torch.arange(k + 1, dtype=torch.int64) * n // k
+    u = torch.rand(k, generator=torch.Generator().manual_seed(SEED), dtype=torch.float64)
+    return j[:-1] + (u * (j[1:] - j[:-1]).double()).long()
+
+
+def dump_outputs(out_dir, model, loss):
+    """--dump-outputs DIR: what the last timed step handed its caller, as DIR/<name>.npy (float32) --
+    loss.npy (the step's loss), grads.npy (every trainable parameter's .grad after loss.backward()) and params.npy (the trainable
+    parameters after optimizer.step()), the last two concatenated in model.named_parameters() order.  An array of more than
+    DUMP_MAX_ELEMS elements is written as a fixed sample of that many distinct positions (dump_positions): the same positions for
+    every build, so two builds compare output for output.  Returns the record that goes into the JSON line."""
+    import numpy as np
+    ps = [p for _, p in model.named_parameters() if p.requires_grad]
+    arrays = {'loss': loss.detach().float().reshape(1),
+              'grads': torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().float().reshape(-1) for p in ps]),
+              'params': torch.cat([p.detach().float().reshape(-1) for p in ps])}
+    os.makedirs(out_dir, exist_ok=True)
+    rec = {'dir': os.path.abspath(out_dir), 'arrays': {}}
+    for name, t in arrays.items():
+        n = t.numel()
+        if n > DUMP_MAX_ELEMS:
+            t = t[dump_positions(n, DUMP_MAX_ELEMS).to(t.device)]
+        np.save(os.path.join(out_dir, name + '.npy'), t.cpu().numpy())
+        rec['arrays'][name] = {'elements': n, 'written': t.numel(), 'sampled': n > DUMP_MAX_ELEMS, 'dtype': 'float32'}
+    return rec
+
+
 def self_launch(a, argv):
     """--gpus N > 1 without a launcher: become N ranks (the reference starts one process per GPU,
     Downstream/Text/script/adapter_houlsby.py:58-59, run.py:685).  This parent never touches the GPU: it starts
@@ -443,7 +476,14 @@ def main():
                          "as bf16 + a nibble per element: at least the accuracy of the reference's autocast path, +1.6 %% on the headline step); bf24: a byte per "
                          "element (+2.4 %%); bf16 = round 5's stream; recorded in config.residual_dtype")
     ap.add_argument('--gemm-variant', type=int, default=-1, help='A/B knob of a4r_gemm_variant (include/a4r.h); default: the library default')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step returned (loss, gradients, updated trainable parameters) as '
+                         f'DIR/<name>.npy in float32 (rank 0; arrays over {DUMP_MAX_ELEMS} elements as a fixed seeded sample).  The last timed '
+                         'step then starts from the seeded trainable state, so the outputs repeat from run to run (a training trajectory of fp32 '
+                         'atomic reductions does not)')
     a = ap.parse_args()
+    if a.steps < 1:
+        raise SystemExit('bench.py: --steps must be at least 1')
     if a.real_shaped:
         a.short_titles = a.ragged_histories = True
     # Every A4R_* variable of the environment goes into the JSON line (`env_knobs`): a record made with an A/B knob set says so itself.
@@ -534,6 +574,19 @@ def main():
     ddp = FlatDDP(model, device_ids=[local], output_device=local)     # broadcasts rank 0's state once (run.py:503); frozen weights never move again
     inner = getattr(model, 'model', model)
     eng = inner._engine()                                      # (FlatDDP's broadcast invalidates the packed copies: this is the engine that runs)
+    # --dump-outputs: the LAST timed step starts from the seeded trainable state (parameters; Adam's moments and step count at zero), so it is a
+    # function of the seeded weights, its batch and its dropout counter alone and two runs -- or two builds -- compare output for output.  A
+    # training trajectory does not repeat: the gradient reductions are fp32 atomic sums whose order varies from run to run, and Adam's normalised
+    # update and the bf16 repack of the fp32 master weights grow those rounding differences step after step.  Every other step trains on as
+    # without the flag; the restore (one copy of the flat parameter buffer, two fills) sits once in the timed region, before the last step.
+    dump_state = eng.flat_p.clone() if a.dump_outputs else None
+
+    def restore_dump_state():
+        eng.flat_p.copy_(dump_state)                           # train_forward repacks the kernel-side copies from flat_p
+        if opt._bound is not None:
+            opt._m.zero_()
+            opt._v.zero_()
+            opt._step = 0
 
     def step(i, api=False):
         items, mask = batches[i % len(batches)]
@@ -557,12 +610,19 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i in range(a.steps):
+        if dump_state is not None and i == a.steps - 1:
+            restore_dump_state()
         loss = step(a.warmup + i)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    # what the LAST timed step returned, taken before the burst / instrumented steps below move the parameters on (outside the timed region)
+    dumped = dump_outputs(a.dump_outputs, model, loss) if (a.dump_outputs and rank == 0) else None
+    if dumped is not None:
+        dumped['last_timed_step_from'] = ('the seeded trainable state: parameters restored, Adam moments and step count reset, once inside the '
+                                          'timed region before the last timed step; the other timed steps train on as without --dump-outputs')
     # host time to ENQUEUE a step (nothing in a step waits for the device): a short burst behind the timed region, from an idle device -- over the K timed
     # steps the host is throttled by the full launch queue and its clock only mirrors the device's.  host >= device means the step is host-bound.
     nb = min(8, a.steps)
@@ -786,6 +846,8 @@ def main():
         }
         if host_leg is not None:
             out['host_images'] = host_leg
+        if dumped is not None:
+            out['dump_outputs'] = dumped
         print(json.dumps(out))
     if world > 1:
         dist.barrier()                 # rank 0 ran its instrumented pass alone: leave the group together
