@@ -12,7 +12,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('A4R_LIB_PATH') or os.path.join(_HERE, 'liba4r_hip.so')    # A4R_LIB_PATH: A/B builds (tools/), same C ABI
 
-ABI_VERSION = 409          # = A4R_ABI_VERSION of include/a4r.h (tests/test_abi_cpu.py compares the two)
+ABI_VERSION = 410          # = A4R_ABI_VERSION of include/a4r.h (tests/test_abi_cpu.py compares the two)
 BF16, F32, FP8 = 0, 1, 2
 ACT_NONE, ACT_RELU, ACT_GELU, ACT_GELU_TANH, ACT_LEAKY = 0, 1, 2, 3, 4
 DACT_MUL = 15
@@ -27,8 +27,9 @@ EXPORTS = [
     'a4r_score_bce_bwd', 'a4r_emb_grad_add_inputs', 'a4r_take_inputs', 'a4r_adam_step', 'a4r_pack_matrices',
     'a4r_eval_rank', 'a4r_dropout_apply', 'a4r_gemm_variant', 'a4r_gemm_tail_plan', 'a4r_gemm_tail_max', 'a4r_gemm_rows_256', 'a4r_adapter_ln_fwd', 'a4r_adapter_ln_bwd', 'a4r_ln_fwd_fp8', 'a4r_ln_fwd_sum', 'a4r_quant_rows_fp8', 'a4r_lora_merge', 'a4r_lora_merge_batch', 'a4r_lora_bwd_fused', 'a4r_lora_bwd_fused_ws_floats', 'a4r_phm_build', 'a4r_phm_bwd', 'a4r_unpack_add', 'a4r_memset_zero',
     'a4r_sasrec_block_fwd', 'a4r_sasrec_block_bwd', 'a4r_scatter_rows_fill', 'a4r_attn_long_fwd', 'a4r_attn_long_bwd', 'a4r_patchify', 'a4r_vit_assemble', 'a4r_resample_u8', 'a4r_embed_bwd', 'a4r_mae_keep_indices',
-    'a4r_encoder_layer_fwd', 'a4r_encoder_layer_bwd',
+    'a4r_encoder_layer_fwd', 'a4r_encoder_layer_bwd', 'a4r_id_index', 'a4r_id_index_ws_ints', 'a4r_id_grad_sum',
 ]
+ID_SUM_CHUNK = 16          # A4R_ID_SUM_CHUNK (include/a4r.h)
 
 
 class GemmArgs(C.Structure):
@@ -512,6 +513,33 @@ def rows_idx_copy(src, dst, idx, n, scatter=False):
     es = src.element_size()
     _check(lib().a4r_rows_idx_copy(_stream(), _p(src), C.c_int64(src.stride(0) * es), _p(dst), C.c_int64(dst.stride(0) * es), _p(idx), C.c_int(n),
                                    C.c_int64(src.shape[1] * es), C.c_int(int(scatter))), 'a4r_rows_idx_copy')
+
+
+def id_index_ws_ints(n, item_num):
+    """int32 elements of a4r_id_index's workspace (a host-side query, no GPU)."""
+    k = int(lib().a4r_id_index_ws_ints(C.c_int(n), C.c_int(item_num)))
+    if k < 0:
+        raise RuntimeError(f'a4r_id_index: n = {n}, item_num = {item_num} outside the supported range (include/a4r.h)')
+    return k
+
+
+def id_index(ids, item_num, rows, slots, ptr, uniq, n_uniq, err, ws):
+    """a4r_id_index over the n = ids.numel() slot ids (int64, device): rows [n], slots [n], ptr [n + 1], uniq [n], n_uniq [1], err [1] int32 outputs."""
+    require_gpu(ids, rows, slots, ptr, uniq, n_uniq, err, ws)
+    n = ids.numel()
+    assert ids.dtype == torch.int64 and ids.is_contiguous() and ws.dtype == torch.int32
+    assert all(t.dtype == torch.int32 for t in (rows, slots, ptr, uniq, n_uniq, err))
+    assert rows.numel() >= n and slots.numel() >= n and ptr.numel() >= n + 1 and uniq.numel() >= n
+    _check(lib().a4r_id_index(_stream(), _p(ids), C.c_int(n), C.c_int(item_num), _p(rows), _p(slots), _p(ptr), _p(uniq), _p(n_uniq), _p(err),
+                              _p(ws), C.c_int64(ws.numel())), 'a4r_id_index')
+
+
+def id_grad_sum(src, slots, ptr, uniq, n_uniq, n, grad):
+    """grad[uniq[u]] += the ordered chunked sum of src[slots[ptr[u] .. ptr[u + 1])] for u < *n_uniq (a4r_id_grad_sum); src, grad fp32 2-D."""
+    require_gpu(src, slots, ptr, uniq, n_uniq, grad)
+    assert src.dtype == torch.float32 and grad.dtype == torch.float32 and src.shape[1] == grad.shape[1] and src.shape[0] >= n
+    _check(lib().a4r_id_grad_sum(_stream(), _p(src), C.c_int(_ld(src)), _p(slots), _p(ptr), _p(uniq), _p(n_uniq), C.c_int(n), _p(grad),
+                                 C.c_int(_ld(grad)), C.c_int(grad.shape[1])), 'a4r_id_grad_sum')
 
 
 def scatter_rows(src, dst, n, row_step):

@@ -81,6 +81,15 @@ def open_image_db(path):
         return LmdbReader(path)
 
 
+def get_itemId_embeddings(model, item_num, test_batch_size, args, local_rank):
+    """metrics.py:52-63 (--item_tower id): the item embeddings ARE the ID table, rows 0 .. item_num -> fp32 [item_num + 1, E] on the device, on
+    every rank (the reference computes it on every rank: no sweep, no all-gather)."""
+    model.eval()
+    emb = _inner(model, args)._engine().table_copy()
+    assert emb.shape[0] == item_num + 1, (tuple(emb.shape), item_num)
+    return emb
+
+
 def get_itemLMDB_embeddings(model, item_num, item_id_to_keys, test_batch_size, args, local_rank, db=None):
     """metrics.py:68-82: encode items 0..item_num (0 = the all-zero pad image, dataset.py:163-166) -> fp32 [N + 1, E] on the device."""
     model.eval()

@@ -6,6 +6,9 @@ the reference's image path (Downstream/CV/model/model.py, encoders.py) -- the dr
     layer.attention.output = VITAdaptedSelfOutput(layer.attention.output, args)                          # :428-434
     loss = model(sample_items.view(-1, 3, R, R), log_mask, local_rank); loss.backward()                   # :582-594
 
+With ``use_modal=False`` (``--item_tower id``) the item tower is the reference's ``id_embedding`` table (model.py:33-35, 55-58): the IDRec
+baseline, trained with the user tower by adapter4rec_amd/engine_id.py.
+
 ``sample_items`` may also be raw uint8 pixels [n, R, R, 3] (the LMDB record content, data_utils/dataset.py:17-27): the
 ToTensor + Normalize(0.5, 0.5) half of the reference's CPU transform then runs inside the patch kernel."""
 import torch
@@ -51,10 +54,8 @@ class MAE_Encoder(nn.Module):                    # encoders.py:8-22
 class _CVBase(nn.Module):
     arch = 'sasrec'
 
-    def __init__(self, args, item_num, use_modal, image_net):
+    def __init__(self, args, item_num, use_modal, image_net=None):
         super().__init__()
-        if not use_modal:
-            raise NotImplementedError('ID tower (use_modal=False) is out of scope')
         self.args = args
         self.use_modal = use_modal
         self.max_seq_len = args.max_seq_len
@@ -62,6 +63,16 @@ class _CVBase(nn.Module):
         self.user_encoder = User_Encoder(item_num=item_num, max_seq_len=args.max_seq_len, item_dim=args.embedding_dim,
                                          num_attention_heads=args.num_attention_heads, dropout=args.drop_rate,
                                          n_layers=args.transformer_block)
+        self.user_encoder._owner[0] = self
+        self._native = [None]
+        self._phm_owner = [None]
+        self.compute_dtype = getattr(args, 'compute_dtype', 'bf16')
+        if not use_modal:                        # model.py:33-35: the IDRec baseline's learned item table (engine_id.py)
+            self.id_embedding = nn.Embedding(item_num + 1, args.embedding_dim, padding_idx=0)
+            xavier_normal_(self.id_embedding.weight.data)
+            self.criterion = nn.BCEWithLogitsLoss()
+            self.register_load_state_dict_post_hook(lambda module, incompatible: module.invalidate_native())
+            return
         name = args.CV_model_load
         if 'mae' in name:                        # model.py:29-30
             self.cv_encoder = MAE_Encoder(image_net=image_net, item_dim=args.embedding_dim)
@@ -71,16 +82,15 @@ class _CVBase(nn.Module):
             raise NotImplementedError(f'--CV_model_load {name}: the native image tower covers ViT and ViT-MAE (resnet/beit/swin are not in the BASELINE configs)')
         self.criterion = nn.BCEWithLogitsLoss()
         self.cv_encoder._owner[0] = self
-        self.user_encoder._owner[0] = self
-        self._native = [None]
-        self._phm_owner = [None]
-        self.compute_dtype = getattr(args, 'compute_dtype', 'bf16')
         self.register_load_state_dict_post_hook(lambda module, incompatible: module.invalidate_native())
 
     def invalidate_native(self):
         self._native[0] = None
 
     def _engine(self):
+        if self._native[0] is None and not self.use_modal:
+            from ..engine_id import IdRecEngine
+            self._native[0] = IdRecEngine(self, self.args, arch=self.arch, dtype=self.compute_dtype)
         if self._native[0] is None:
             from ..engine_vit import ViTRecEngine
             self._native[0] = ViTRecEngine(self, self.args, arch=self.arch, dtype=self.compute_dtype, phm_owner=self._phm_owner[0])
@@ -89,7 +99,7 @@ class _CVBase(nn.Module):
     def item_encoder_in(self, dtype):
         """items -> embeddings computed in `dtype` on the current weights (a forward-only snapshot engine; eval's item sweep in
         fp32 while training runs in bf16: data_utils/metrics.py get_item_embeddings, --eval_compute_dtype)."""
-        if dtype == self.compute_dtype:
+        if dtype == self.compute_dtype or not self.use_modal:          # (the ID table is fp32 whatever the compute dtype)
             return self._engine().encode_items
         from ..engine_vit import ViTRecEngine
         snap = ViTRecEngine.inference_snapshot(self, self.args, self.arch, dtype, self._phm_owner[0])
@@ -100,6 +110,7 @@ class _CVBase(nn.Module):
         return super()._apply(fn, *a, **k)
 
     def forward(self, sample_items, log_mask, local_rank=None, noise=None):
+        """sample_items: images (use_modal) or the flat int64 slot ids [B * (L + 1) * 2] of the ID tower, on the host or the device."""
         eng = self._engine()
         eng.next_noise = noise                   # ViT-MAE: explicit masking noise [n, n_patches] (parity runs); None = drawn on device
         if not log_mask.is_cuda:                 # host log_mask: the batch's pad structure, read without a sync (model/model.py)

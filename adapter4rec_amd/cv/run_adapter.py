@@ -16,12 +16,13 @@ import torch
 import torch.distributed as dist
 from torch.utils.data import DataLoader
 
+from ..data_utils.dataset import BuildTrainDataset
 from ..data_utils.utils import get_checkpoint, para_and_log, report_time_eval, report_time_train, save_model, setuplogger
 from ..ddp import FlatDDP, any_rank
 from ..inject import freeze_all
 from ..optim import FusedAdam
 from . import Model, ModelCPC, ViTForImageClassification, ViTMAEModel
-from .data_utils import eval_model, get_itemLMDB_embeddings, open_image_db, read_behaviors, read_images
+from .data_utils import eval_model, get_itemId_embeddings, get_itemLMDB_embeddings, open_image_db, read_behaviors, read_images
 from .image_io import Build_Lmdb_Dataset, assemble_batch, collate_host
 from .inject import inject_adapters, optimizer_groups
 from .parameters import parse_args
@@ -62,6 +63,14 @@ def load_backbone(args, Log_file):
     return net
 
 
+def check_id_flags(args):
+    """--item_tower id (the IDRec baseline) trains the whole model: the reference's other flag combinations freeze everything or walk cv_encoder,
+    which the ID tower does not have (run_adapter.py:365-440)."""
+    if args.fine_tune_to != 'all' or args.adding_adapter_to != 'None':
+        raise ValueError(f'--item_tower id needs --fine_tune_to all and --adding_adapter_to None '
+                         f'(got --fine_tune_to {args.fine_tune_to} --adding_adapter_to {args.adding_adapter_to})')
+
+
 def build_model(args, item_num, use_modal, cv_model, local_rank, Log_file, model_dir):
     model = (ModelCPC if 'cpc' in args.arch else Model)(args, item_num, use_modal, cv_model)
     if 'None' not in args.pretrained_recsys_model:                    # :341-350
@@ -92,7 +101,10 @@ def build_model(args, item_num, use_modal, cv_model, local_rank, Log_file, model
 def run_eval_once(model, db, item_id_to_keys, user_history, users_eval, batch_size, item_num, mode, local_rank, args, Log_file):
     t0 = time.time()
     Log_file.info('Validating...')
-    emb = get_itemLMDB_embeddings(model, item_num, item_id_to_keys, batch_size, args, local_rank, db=db)
+    if db is None:                                                     # --item_tower id: the table itself (run_adapter.py:275-279)
+        emb = get_itemId_embeddings(model, item_num, batch_size, args, local_rank)
+    else:
+        emb = get_itemLMDB_embeddings(model, item_num, item_id_to_keys, batch_size, args, local_rank, db=db)
     hit10 = eval_model(model, user_history, users_eval, emb, batch_size, args, item_num, Log_file, mode, local_rank)
     report_time_eval(t0, Log_file)
     return hit10
@@ -103,19 +115,31 @@ def _collate(batch):
 
 
 def train(args, use_modal, local_rank, Log_file, Log_screen, model_dir, start_time):
-    cv_model = load_backbone(args, Log_file)
+    if not use_modal:
+        check_id_flags(args)
+    cv_model = load_backbone(args, Log_file) if use_modal else None       # --item_tower id: no backbone, no image database
     before_keys, before_name2id = read_images(os.path.join(args.root_data_dir, args.dataset, args.images))
     item_num, item_id_to_keys, users_train, users_valid, users_test, hist_valid, hist_test = read_behaviors(
         os.path.join(args.root_data_dir, args.dataset, args.behaviors), before_keys, before_name2id, args.max_seq_len,
         args.min_seq_len, Log_file)
-    db = open_image_db(os.path.join(args.root_data_dir, args.dataset, args.lmdb_data))
+    db = open_image_db(os.path.join(args.root_data_dir, args.dataset, args.lmdb_data)) if use_modal else None
     # --num_workers n > 0 (the reference's DataLoader pool, run_adapter.py:448-450; its 12 workers do PIL resizing on the CPU): the workers decode the
     # records and stack them by source size (no device in a worker), the pinned batches are uploaded, resized and scattered on the GPU here
     # (image_io.assemble_batch) while the previous step computes.  --num_workers 0: decode in this process.
-    host = args.num_workers > 0
-    train_dataset = Build_Lmdb_Dataset(users_train, item_num, args.max_seq_len, db, item_id_to_keys, args.CV_resize, device=f'cuda:{local_rank}', host=host)
+    host = args.num_workers > 0 and use_modal
+    if not use_modal:                                                  # run_adapter.py:316-321: Build_Id_Dataset (ids, the same negative draw)
+        train_dataset = BuildTrainDataset(users_train, None, item_num, args.max_seq_len, use_modal=False)
+    else:
+        train_dataset = Build_Lmdb_Dataset(users_train, item_num, args.max_seq_len, db, item_id_to_keys, args.CV_resize, device=f'cuda:{local_rank}', host=host)
     sampler = torch.utils.data.distributed.DistributedSampler(train_dataset)
-    if host:
+    if not use_modal and args.num_workers > 0:
+        def worker_init(worker_id):                                    # (the worker seeding of the image path below)
+            seed = torch.initial_seed() % 2 ** 31 + worker_id + dist.get_rank()
+            random.seed(seed)
+            np.random.seed(seed)
+        train_dl = DataLoader(train_dataset, batch_size=args.batch_size, num_workers=args.num_workers, sampler=sampler, collate_fn=_collate,
+                              worker_init_fn=worker_init, pin_memory=True)
+    elif host:
         # The workers draw the negatives (Python `random`, Build_Lmdb_Dataset.__getitem__): reseeded as the reference does (run_adapter.py:326-334)
         # from the worker's torch seed + worker id + rank.  NOT persistent: every epoch's iterator takes a fresh base seed from the torch generator
         # -- the state a checkpoint holds (utils.py:109-115) --, so a resumed run's workers draw what the uninterrupted run's would have, and two
@@ -150,9 +174,12 @@ def train(args, use_modal, local_rank, Log_file, Log_screen, model_dir, start_ti
         # the iterator's base seed (worker_init above) -- the text entry point's arrangement.
         random.seed(int(torch.randint(0, 2 ** 31 - 1, (1,)).item()))
         for sample_items, log_mask in train_dl:
-            if host:
+            if not use_modal:
+                sample_items = sample_items.view(-1)                   # int64 ids on the host (run_adapter.py:581-584); the engine uploads them
+            elif host:
                 sample_items = assemble_batch(sample_items, log_mask.shape[0], args.max_seq_len + 1, R, torch.device('cuda', local_rank))
-            sample_items = sample_items.view(-1, R, R, 3)              # uint8 HWC (the reference: .view(-1, 3, R, R) of fp32)
+            if use_modal:
+                sample_items = sample_items.view(-1, R, R, 3)          # uint8 HWC (the reference: .view(-1, 3, R, R) of fp32)
             optimizer.zero_grad()                                      # (log_mask stays on the host: Model.forward uploads it, the engine reads the pad slots from it)
             bz_loss = model(sample_items, log_mask, local_rank)
             loss += bz_loss.detach()
@@ -183,12 +210,14 @@ def train(args, use_modal, local_rank, Log_file, Log_screen, model_dir, start_ti
 
 
 def test(args, use_modal, local_rank, Log_file, Log_screen, model_dir, start_time):
-    cv_model = load_backbone(args, Log_file)
+    if not use_modal:
+        check_id_flags(args)
+    cv_model = load_backbone(args, Log_file) if use_modal else None
     before_keys, before_name2id = read_images(os.path.join(args.root_data_dir, args.dataset, args.images))
     item_num, item_id_to_keys, _, users_valid, users_test, hist_valid, hist_test = read_behaviors(
         os.path.join(args.root_data_dir, args.dataset, args.behaviors), before_keys, before_name2id, args.max_seq_len,
         args.min_seq_len, Log_file)
-    db = open_image_db(os.path.join(args.root_data_dir, args.dataset, args.lmdb_data))
+    db = open_image_db(os.path.join(args.root_data_dir, args.dataset, args.lmdb_data)) if use_modal else None
     model, _, _ = build_model(args, item_num, use_modal, cv_model, local_rank, Log_file, model_dir)
     model = FlatDDP(model, device_ids=[local_rank], output_device=local_rank)
     run_eval_once(model, db, item_id_to_keys, hist_valid, users_valid, 256, item_num, 'valid', local_rank, args, Log_file)

@@ -2110,6 +2110,25 @@ class TransRecEngine:
         """Native backward of the last train_forward.  into_flat_grad: accumulate straight into the flat
         gradient buffer (fused path); else into the scratch buffer, returned as per-parameter gradients for autograd to
         accumulate (as_list).  grad_out: d(loss) as a 0-d fp32 DEVICE tensor (read by the head kernel, no host sync)."""
+        c, target, d_emb = self._head_user_backward(grad_out, into_flat_grad)
+        B, n_items, n_full = c['B'], c['n_items'], c.get('n_full', c['n_items'])
+        if n_full != n_items:
+            Ip = pad_to(n_items, 128)
+            d_emb_c = self._buf_tail0('d_emb_c', Ip, self.E, torch.float32, n_items)
+            self._slots_copy(d_emb, d_emb_c, B, True, c.get('kidx'))
+            d_emb = d_emb_c
+        else:
+            Ip = pad_to(n_full, 128)
+        if self.n_attr > 1:                        # the mean over the news attributes: every attribute's rows get d_emb / n_attr
+            d_emb, Ip = self._attr_spread(d_emb, n_items)
+            c = dict(c, n_items=c['n_enc'])
+        self._items_backward(c, d_emb, Ip)
+        return self._backward_finish(target, into_flat_grad, as_list)
+
+    def _head_user_backward(self, grad_out, into_flat_grad):
+        """The part of backward every item tower shares: the scoring head, the user tower (last block to first), its input LayerNorm and
+        position table, and the input-side rows of d_emb; the user tower's chunk is then handed to the data-parallel exchange.
+        -> (the forward's context, the gradient target, d_emb [pad_to(n_full, 128), E] fp32: one row per slot of the [B, L, 2] layout)."""
         c = self._ctx
         if c is None:
             raise RuntimeError('train_backward without train_forward')
@@ -2170,15 +2189,10 @@ class TransRecEngine:
             self.g_pos_emb()[:Tn].add_(d_in[:B * Tn].view(B, Tn, E).sum(0))
         L.emb_grad_add_inputs(d_in, d_emb, B, self.Lseq, E)
         self._exchange('user')
-        if n_full != n_items:
-            Ip = pad_to(n_items, 128)
-            d_emb_c = self._buf_tail0('d_emb_c', Ip, E, torch.float32, n_items)
-            self._slots_copy(d_emb, d_emb_c, B, True, c.get('kidx'))
-            d_emb = d_emb_c
-        if self.n_attr > 1:                        # the mean over the news attributes: every attribute's rows get d_emb / n_attr
-            d_emb, Ip = self._attr_spread(d_emb, n_items)
-            c = dict(c, n_items=c['n_enc'])
-        self._items_backward(c, d_emb, Ip)
+        return c, target, d_emb
+
+    def _backward_finish(self, target, into_flat_grad, as_list):
+        """After the item tower's backward: side-stream joins, scratch corners, virtual adapters; the per-parameter list (autograd path)."""
         self._wgrad_join()
         self._flush_corners()
         if self._virtual:

@@ -44,7 +44,7 @@ extern "C" {
 
 /* ABI version: bumped whenever a signature or struct below changes.  The Python binding (adapter4rec_amd/_lib.py) refuses a
  * library whose a4r_version() differs, so an A/B build made before a signature change cannot be called with shifted arguments. */
-#define A4R_ABI_VERSION 409
+#define A4R_ABI_VERSION 410
 int a4r_version(void);
 
 /* C[M,N] = epilogue(alpha * A[M,K] . B[N,K]^T): every nn.Linear on the path (HF BertSelfAttention
@@ -457,6 +457,25 @@ int a4r_memset_zero(void* stream, void* p, int64_t bytes);
 #define A4R_EVAL_MAX_HISTORY 264
 int a4r_eval_rank(void* stream, const float* prec, const float* item_emb, const int32_t* target,
                   const int32_t* hist_ptr, const int32_t* hist_idx, int32_t* rank, int U, int N1, int E);
+
+/* The learned item-ID table of the IDRec baseline (ABI 410; Downstream/CV/model/model.py: nn.Embedding(item_num + 1, E, padding_idx=0), fed the flat
+ * slot ids of a batch).  a4r_id_index, once per step: rows[i] = ids[i] when 0 <= ids[i] <= item_num, else 0 and counted in *err (overwritten: the
+ * number of such slots in this call) -- rows is what a4r_rows_idx_copy gathers the table with.  The inverted index in CSR form: *n_uniq distinct
+ * ids 1 .. item_num occur, uniq[u] (ascending) is the u-th, its slots are slots[ptr[u] .. ptr[u + 1]) in ascending slot order, ptr[*n_uniq] = n.
+ * Slots reading row 0 (padding_idx) or out of range are in no list (they sit in front of ptr[0]).  slots [n], ptr [n + 1], uniq [n] int32.
+ * Integer work only (a stable radix sort of the slots by id); nothing of it is read back on the host.  n <= 2^20, 0 < item_num < 2^31 - 1,
+ * else A4R_EINVAL.  ws: a4r_id_index_ws_ints(n, item_num) int32 of device scratch (contents need not be kept between calls). */
+int a4r_id_index(void* stream, const int64_t* ids, int n, int item_num, int32_t* rows, int32_t* slots, int32_t* ptr, int32_t* uniq,
+                 int32_t* n_uniq, int32_t* err, int32_t* ws, int64_t ws_ints);
+int a4r_id_index_ws_ints(int n, int item_num);
+/* a4r_id_grad_sum: for every list u < *n_uniq, grad[uniq[u], :] += S_u, where S_u is the sum of the src rows of its slots in this exact order: the
+ * list is cut into consecutive chunks of A4R_ID_SUM_CHUNK slots, each chunk summed sequentially in list order from 0.0f, the chunk sums added
+ * sequentially in chunk order, the row of grad read and written once.  No float atomics: the result is a function of the inputs alone.  Rows in
+ * no list are not touched.  src fp32 [>= n, ld_src], grad fp32 [item_num + 1, ldg]; E % 4 == 0, E <= 1024, both 16-byte aligned (ld % 4 == 0).
+ * The chunk bounds the serial part of a skewed list: one wave sums a list, four chunks at a time, and a chunk's loads are issued together. */
+#define A4R_ID_SUM_CHUNK 16
+int a4r_id_grad_sum(void* stream, const float* src, int ld_src, const int32_t* slots, const int32_t* ptr, const int32_t* uniq,
+                    const int32_t* n_uniq, int n, float* grad, int ldg, int E);
 
 /* ONE post-LN encoder layer per call (ABI 409; SURVEY 8(b) `encoder_layer_fwd / bwd`): HF BertLayer with the reference's serial Houlsby wrappers on
  * both sub-layers (Downstream/Text/model/model.py:292-297 on attention.output and output, injected at run.py:452-465), frozen backbone.  The call

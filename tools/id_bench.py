@@ -1,0 +1,132 @@
+#!/usr/bin/env python
+"""Throughput of the ID item tower (--item_tower id, the IDRec baseline) on its public path: optimizer.zero_grad(), model(ids, log_mask),
+loss.backward(), FusedAdam.step() -- one JSON line per configuration (ms/step, user-seq/s, and the inverted index's list lengths of a batch).
+
+    python tools/id_bench.py [--steps K] [--warmup W] [--only NAME]
+
+Configurations (the reference's CV defaults: B 64, E 64, 2 blocks x 2 heads, Downstream/CV/parameters.py):
+  full_L10 / full_L20     full histories at --max_seq_len 10 / 20, item_num 14 720 (the Amazon 2w catalogue), ids uniform
+  real_L20                the 1 024 real user sequences of tests/golden/real_data/amazon_users_head.tsv (real lengths, real repeats), 64 per batch
+  full_L20_500k           item_num 500 000: what dense Adam and zero_grad cost over a large table
+Per-kernel times: run this under `rocprofv3 --kernel-trace --stats -- python tools/id_bench.py`."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+B, E = 64, 64
+
+
+def model_args(max_seq_len):
+    return argparse.Namespace(max_seq_len=max_seq_len, l2_weight=0, embedding_dim=E, num_attention_heads=2, drop_rate=0.1, transformer_block=2,
+                              CV_model_load='vit-base-patch16-224', compute_dtype='bf16', arch='sasrec')
+
+
+def batch_from_seqs(seqs, L, item_num, rng):
+    """BuildTrainDataset(use_modal=False) for a list of user sequences (left padded, one uniform negative per real position outside the
+    user's sequence) -> (host int64 ids [B * L * 2], host log_mask [B, L - 1])."""
+    ids = np.zeros((len(seqs), L, 2), np.int64)
+    mask = np.zeros((len(seqs), L - 1), np.float32)
+    for u, seq in enumerate(seqs):
+        seq = list(seq)[-L:]
+        n = len(seq)
+        own = set(seq)
+        negs = []
+        while len(negs) < n - 1:
+            s = int(rng.integers(1, item_num + 1))
+            if s not in own:
+                negs.append(s)
+        ids[u, L - n:, 0] = seq
+        ids[u, L - n:L - 1, 1] = negs
+        mask[u, L - n:] = 1.0
+    return torch.from_numpy(ids.reshape(-1)), torch.from_numpy(mask)
+
+
+def real_seqs():
+    """tests/golden/real_data/amazon_users_head.tsv: item names renumbered 1.. in order of first appearance."""
+    ids, out = {}, []
+    with open(os.path.join(ROOT, 'tests', 'golden', 'real_data', 'amazon_users_head.tsv')) as f:
+        for line in f:
+            names = line.rstrip('\n').split('\t')[1].split(' ')
+            out.append([ids.setdefault(nm, len(ids) + 1) for nm in names])
+    return out
+
+
+def list_stats(ids):
+    """Lengths of the inverted index's lists (slots per distinct non-zero id) of one batch."""
+    v = ids.numpy()
+    _, c = np.unique(v[v > 0], return_counts=True)
+    return dict(slots=int(v.size), distinct=int(c.size), longest_list=int(c.max()), median_list=float(np.median(c)),
+                p99_list=float(np.quantile(c, 0.99)))
+
+
+def make_batches(name, L, item_num, n_batches, rng):
+    if name.startswith('real'):
+        seqs = real_seqs()
+        order = rng.permutation(len(seqs))
+        return [batch_from_seqs([seqs[i] for i in order[k * B:(k + 1) * B]], L, item_num, rng) for k in range(n_batches)]
+    return [batch_from_seqs([rng.integers(1, item_num + 1, L) for _ in range(B)], L, item_num, rng) for _ in range(n_batches)]
+
+
+def run(name, max_seq_len, item_num, steps, warmup):
+    from adapter4rec_amd.cv import Model
+    from adapter4rec_amd.cv.inject import optimizer_groups
+    from adapter4rec_amd.optim import FusedAdam
+    torch.manual_seed(0)
+    rng = np.random.default_rng(0)
+    args = model_args(max_seq_len)
+    args.lr, args.fine_tune_lr, args.adapter_cv_lr, args.adapter_sasrec_lr = 1e-4, 1e-4, 1e-4, 1e-4
+    model = Model(args, item_num, False).to('cuda')
+    model.train()
+    opt = FusedAdam(optimizer_groups(model, args))
+    L = max_seq_len + 1
+    batches = make_batches(name, L, item_num, 16, rng)
+    stats = list_stats(batches[0][0])
+    lens = [list_stats(b[0]) for b in batches]
+
+    def step(i):
+        items, mask = batches[i % len(batches)]
+        opt.zero_grad()
+        loss = model(items, mask, 0)
+        loss.backward()
+        opt.step()
+        return loss
+
+    for i in range(warmup):
+        step(i)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for i in range(steps):
+        loss = step(i)
+    torch.cuda.synchronize()
+    dt = (time.perf_counter() - t0) / steps
+    return dict(config=name, batch=B, embedding_dim=E, max_seq_len=max_seq_len, item_num=item_num, steps=steps, warmup=warmup,
+                ms_per_step=round(dt * 1e3, 4), user_seq_per_s=round(B / dt, 1), loss=float(loss.detach()),
+                longest_list_max=max(s['longest_list'] for s in lens), median_list_median=float(np.median([s['median_list'] for s in lens])),
+                first_batch=stats)
+
+
+CONFIGS = [('full_L10', 10, 14720), ('full_L20', 20, 14720), ('real_L20', 20, 14720), ('full_L20_500k', 20, 500000)]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--steps', type=int, default=200)
+    ap.add_argument('--warmup', type=int, default=20)
+    ap.add_argument('--only', default=None)
+    a = ap.parse_args()
+    for name, msl, n in CONFIGS:
+        if a.only and name != a.only:
+            continue
+        print(json.dumps(run(name, msl, n, a.steps, a.warmup)), flush=True)
+
+
+if __name__ == '__main__':
+    main()
