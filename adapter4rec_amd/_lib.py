@@ -12,7 +12,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('A4R_LIB_PATH') or os.path.join(_HERE, 'liba4r_hip.so')    # A4R_LIB_PATH: A/B builds (tools/), same C ABI
 
-ABI_VERSION = 410          # = A4R_ABI_VERSION of include/a4r.h (tests/test_abi_cpu.py compares the two)
+ABI_VERSION = 411          # = A4R_ABI_VERSION of include/a4r.h (tests/test_abi_cpu.py compares the two)
 BF16, F32, FP8 = 0, 1, 2
 ACT_NONE, ACT_RELU, ACT_GELU, ACT_GELU_TANH, ACT_LEAKY = 0, 1, 2, 3, 4
 DACT_MUL = 15
@@ -28,8 +28,11 @@ EXPORTS = [
     'a4r_eval_rank', 'a4r_dropout_apply', 'a4r_gemm_variant', 'a4r_gemm_tail_plan', 'a4r_gemm_tail_max', 'a4r_gemm_rows_256', 'a4r_adapter_ln_fwd', 'a4r_adapter_ln_bwd', 'a4r_ln_fwd_fp8', 'a4r_ln_fwd_sum', 'a4r_quant_rows_fp8', 'a4r_lora_merge', 'a4r_lora_merge_batch', 'a4r_lora_bwd_fused', 'a4r_lora_bwd_fused_ws_floats', 'a4r_phm_build', 'a4r_phm_bwd', 'a4r_unpack_add', 'a4r_memset_zero',
     'a4r_sasrec_block_fwd', 'a4r_sasrec_block_bwd', 'a4r_scatter_rows_fill', 'a4r_attn_long_fwd', 'a4r_attn_long_bwd', 'a4r_patchify', 'a4r_vit_assemble', 'a4r_resample_u8', 'a4r_embed_bwd', 'a4r_mae_keep_indices',
     'a4r_encoder_layer_fwd', 'a4r_encoder_layer_bwd', 'a4r_id_index', 'a4r_id_index_ws_ints', 'a4r_id_grad_sum',
+    'a4r_topk_items',
 ]
 ID_SUM_CHUNK = 16          # A4R_ID_SUM_CHUNK (include/a4r.h)
+TOPK_MAX_K = 256           # A4R_TOPK_MAX_K (include/a4r.h)
+TOPK_E = (64, 128, 256, 512)
 
 
 class GemmArgs(C.Structure):
@@ -108,6 +111,7 @@ def lib():
         _lib = C.CDLL(LIB_PATH)
         for name in EXPORTS:
             getattr(_lib, name).restype = C.c_int
+        _lib.a4r_topk_ws_bytes.restype = C.c_size_t        # (the one size_t-valued export; not in EXPORTS, whose entries return a status)
         got = _lib.a4r_version()
         if got != ABI_VERSION:        # an older A/B build has every export but other argument lists: calling it would pass shifted pointers
             _lib = None
@@ -683,6 +687,48 @@ def adam_step(p, g, m, v, seg_end, seg_group, group_lr, step, beta1=0.9, beta2=0
 def pack_matrices(flat, desc_dev, n_desc, max_elems, dtype):
     _check(lib().a4r_pack_matrices(_stream(), _p(flat), _p(desc_dev), C.c_int(n_desc), C.c_int(max_elems), C.c_int(dtype)),
            'a4r_pack_matrices')
+
+
+def topk_ws_bytes(U, N1, k):
+    """Bytes of a4r_topk_items' workspace (a host-side query, no GPU); 0 for a shape the kernel refuses."""
+    return int(lib().a4r_topk_ws_bytes(C.c_int(U), C.c_int(N1), C.c_int(k)))
+
+
+def topk_items(prec, item_emb, excl_ptr, excl_idx, k, ids, scores):
+    """a4r_topk_items: ids [U, k] int32 / scores [U, k] fp32 = the k best items 1 .. N1-1 of every user, excluding the user's CSR list
+    excl_idx[excl_ptr[u] .. excl_ptr[u + 1]) (<= EVAL_MAX_HISTORY ids each: the caller checks, as for eval_rank), by score descending, ties by
+    smaller id; short lists end in id 0 / -inf (include/a4r.h).  The workspace is allocated here."""
+    require_gpu(prec, item_emb, excl_ptr, excl_idx, ids, scores)
+    k = int(k)
+    if prec.dim() != 2 or item_emb.dim() != 2 or prec.shape[1] != item_emb.shape[1]:
+        raise ValueError(f'topk_items: prec [U, E] and item_emb [N1, E] expected, got {tuple(prec.shape)} and {tuple(item_emb.shape)}')
+    U, E = prec.shape
+    N1 = item_emb.shape[0]
+    if prec.dtype != torch.float32 or item_emb.dtype != torch.float32 or not prec.is_contiguous() or not item_emb.is_contiguous():
+        raise ValueError('topk_items: prec and item_emb must be contiguous fp32')
+    if E not in TOPK_E:
+        raise ValueError(f'topk_items: E = {E}, supported {TOPK_E}')
+    if not 1 <= k <= TOPK_MAX_K:
+        raise ValueError(f'topk_items: k = {k} outside 1 .. {TOPK_MAX_K}')
+    if U < 1 or N1 < 2:
+        raise ValueError(f'topk_items: U = {U} users and N1 = {N1} table rows (row 0 = the pad item): need U >= 1, N1 >= 2')
+    if (prec.data_ptr() | item_emb.data_ptr()) & 15:
+        raise ValueError('topk_items: prec and item_emb must be 16-byte aligned')
+    for name, t in (('excl_ptr', excl_ptr), ('excl_idx', excl_idx), ('ids', ids)):
+        if t.dtype != torch.int32 or not t.is_contiguous():
+            raise ValueError(f'topk_items: {name} must be contiguous int32')
+    if scores.dtype != torch.float32 or not scores.is_contiguous():
+        raise ValueError('topk_items: scores must be contiguous fp32')
+    if excl_ptr.numel() != U + 1:
+        raise ValueError(f'topk_items: excl_ptr must hold U + 1 = {U + 1} offsets, got {excl_ptr.numel()}')
+    if tuple(ids.shape) != (U, k) or tuple(scores.shape) != (U, k):
+        raise ValueError(f'topk_items: ids and scores must be [{U}, {k}]')
+    if excl_idx.numel() == 0:                 # (an empty list has no data pointer; the kernel reads no id of it)
+        excl_idx = torch.zeros(1, dtype=torch.int32, device=prec.device)
+    ws = torch.empty(topk_ws_bytes(U, N1, k), dtype=torch.uint8, device=prec.device)
+    _check(lib().a4r_topk_items(_stream(), _p(prec), _p(item_emb), _p(excl_ptr), _p(excl_idx), _p(ids), _p(scores), _p(ws),
+                                C.c_int(U), C.c_int(N1), C.c_int(E), C.c_int(k)), 'a4r_topk_items')
+    return ids, scores
 
 
 def eval_rank(prec, item_emb, target, hist_ptr, hist_idx, rank):

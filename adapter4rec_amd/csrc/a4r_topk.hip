@@ -1,0 +1,271 @@
+// Top-K recommendation: the K best items of every user, history excluded, without materialising the [users, items] score matrix.
+//
+// score(u, i) = <prec[u], item_emb[i]> is formed exactly as a4r_eval_rank forms it (a4r_eval.hip): 16 users per workgroup as the A operand of fp32
+// MFMA 16x16x4 tiles held in registers, the item table streamed 16 rows at a time as the B operand with the next tile's fragments requested one
+// tile ahead, the 4 waves of a workgroup taking every 4th tile of the workgroup's item range.  Same instruction sequence, same bits.
+//
+// Selection.  An item is a 64-bit key  orderable(score) << 32 | ~id : one unsigned compare orders by score descending, then id ascending (NaN maps
+// below -inf, -0 onto +0; key 0 is "no item").  Every user keeps a candidate buffer in LDS and a threshold, the K-th best key the workgroup
+// holds (0 until it holds K).  A key above the threshold is checked against the user's exclusion list (sorted in LDS once, a binary search: the
+// check runs for threshold-beating items only, off the hot loop) and appended.  The 4 waves meet at a barrier once per step of 4 tiles; a step
+// adds at most 64 keys per user, so when any buffer has less than 64 free slots left, all 16 buffers are sorted (bitonic, in LDS) and cut back
+// to K, which raises the thresholds.  At the end of its range the workgroup writes its K best keys per user (sorted) to the workspace.
+//
+// Merge.  A second launch turns the gy sorted lists of a user into the final K: with one item range it decodes the list; with more, every
+// listed key's final position is its position in its own list plus the number of keys above it in the others (binary searches in LDS; keys are
+// unique, so positions are distinct).  Keys are a total order and each item range holds every item of the global top K that falls in it, so
+// the result does not depend on the grid.
+#include "a4r_common.h"
+#include "../../include/a4r.h"
+
+namespace {
+
+constexpr int MAXX = A4R_EVAL_MAX_HISTORY;   // exclusion ids per user kept in LDS (the a4r_eval_rank bound)
+constexpr int STEP_KEYS = 64;                // keys a step can add per user: 4 waves x 16 item columns
+constexpr int MAX_RANGES = 32;               // item ranges per user: the merge holds gy x K <= 32 x 256 keys (64 KiB) in LDS
+
+__device__ __forceinline__ uint64_t topk_key(float s, int id) {
+    uint32_t b = __float_as_uint(s);
+    if (b == 0x80000000u) b = 0u;                                           // -0 == +0: one key
+    uint32_t o = (b & 0x80000000u) ? ~b : (b | 0x80000000u);              // monotone in the float value
+    if (s != s) o = 0u;                                                     // NaN: below -inf
+    return ((uint64_t)o << 32) | (uint32_t)~(uint32_t)id;
+}
+
+__device__ __forceinline__ void topk_emit(uint64_t key, int32_t* id, float* score) {
+    if (key == 0) { *id = 0; *score = -__builtin_huge_valf(); return; }    // short list: pad slot
+    const uint32_t o = (uint32_t)(key >> 32);
+    *id = (int32_t)~(uint32_t)key;
+    *score = o == 0 ? __builtin_nanf("") : __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
+}
+
+// Sort each of the 16 buffers (cap keys, cap a power of two) descending, entries past the count as 0; keep the best K, reset the thresholds.
+__device__ void topk_compact(uint64_t* buf, int cap, int K, int32_t* cnt, uint64_t* thr) {
+    const int tid = threadIdx.x, lc = __builtin_ctz(cap);
+    for (int e = tid; e < 16 * cap; e += 256)
+        if ((e & (cap - 1)) >= cnt[e >> lc]) buf[e] = 0;
+    __syncthreads();
+    for (int k = 2; k <= cap; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int p = tid; p < 8 * cap; p += 256) {                      // 16 users x cap / 2 pairs
+                const int ul = p >> (lc - 1), q = p & ((cap >> 1) - 1);
+                const int a = 2 * q - (q & (j - 1)), b = a + j;
+                uint64_t* row = buf + (ul << lc);
+                const uint64_t x = row[a], y = row[b];
+                if (((a & k) == 0) ? x < y : x > y) { row[a] = y; row[b] = x; }
+            }
+            __syncthreads();
+        }
+    if (tid < 16) {
+        const int c = min(cnt[tid], K);
+        cnt[tid] = c;
+        thr[tid] = c == K ? buf[(tid << lc) + K - 1] : 0;
+    }
+    __syncthreads();
+}
+
+template <int E>
+__global__ void __launch_bounds__(256) topk_partial_kernel(const float* __restrict__ prec, const float* __restrict__ item_emb,
+                                                           const int32_t* __restrict__ excl_ptr, const int32_t* __restrict__ excl_idx,
+                                                           uint64_t* __restrict__ ws, int U, int N1, int K, int cap) {
+    constexpr int KS = E / 16;                       // chunk steps (fp32: 16 k per step)
+    constexpr int PER = (MAXX + 15) / 16;            // exclusion ids per thread while sorting
+    extern __shared__ uint64_t buf[];                // [16][cap] candidate keys
+    __shared__ int32_t excl[16][MAXX];
+    __shared__ int32_t nex[16];
+    __shared__ int32_t cnt[16];
+    __shared__ uint64_t thr_s[16];
+    __shared__ int trig;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int r16 = lane & 15, kg = lane >> 4;
+    const int u0 = blockIdx.x * 16;
+    {   // 16 threads per user copy its exclusion ids, then put them in ascending order (rank of each id among the list, ties by position)
+        const int ul = tid >> 4, j0 = tid & 15, u = min(u0 + ul, U - 1);
+        const int b = excl_ptr[u], n = max(0, min(excl_ptr[u + 1] - b, MAXX));
+        for (int j = j0; j < n; j += 16) excl[ul][j] = excl_idx[b + j];
+        if (j0 == 0) { nex[ul] = n; cnt[ul] = 0; thr_s[ul] = 0; }
+        if (tid == 0) trig = -1;
+        __syncthreads();
+        int v[PER], pos[PER];
+#pragma unroll
+        for (int m = 0; m < PER; ++m) {
+            const int j = j0 + 16 * m;
+            pos[m] = -1; v[m] = 0;
+            if (j < n) {
+                const int x = excl[ul][j];
+                int p = 0;
+                for (int k = 0; k < n; ++k) {
+                    const int y = excl[ul][k];
+                    p += (y < x || (y == x && k < j)) ? 1 : 0;
+                }
+                v[m] = x; pos[m] = p;
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int m = 0; m < PER; ++m)
+            if (pos[m] >= 0) excl[ul][pos[m]] = v[m];
+    }
+    // A operand: 16 users x E, lane (user r16, kg) holds chunk (ks*4 + kg) -- as eval_rank_kernel
+    uint4 ua[KS];
+    const int urow = min(u0 + r16, U - 1);
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) ua[ks] = *reinterpret_cast<const uint4*>(prec + (size_t)urow * E + (ks * 4 + kg) * 4);
+    __syncthreads();
+    const int ntiles = (N1 - 1 + 15) / 16, tstep = gridDim.y * 4;
+    const int first = blockIdx.y * 4;
+    const int nsteps = first < ntiles ? (ntiles - first + tstep - 1) / tstep : 0;     // the same for the 4 waves: they meet at every step's barrier
+    uint64_t thr[4] = {0, 0, 0, 0};
+    bool live[4];
+#pragma unroll
+    for (int rr = 0; rr < 4; ++rr) live[rr] = u0 + kg * 4 + rr < U;
+    int t = first + wave;
+    uint4 bn[KS];
+    {
+        const int irow = min(1 + min(t, ntiles - 1) * 16 + r16, N1 - 1);
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) bn[ks] = *reinterpret_cast<const uint4*>(item_emb + (size_t)irow * E + (ks * 4 + kg) * 4);
+    }
+    for (int s = 0; s < nsteps; ++s, t += tstep) {
+        const int i = 1 + t * 16 + r16;                 // this lane's item column (>= N1 past the end of the table: nothing to add)
+        uint4 b[KS];
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) b[ks] = bn[ks];
+        {
+            const int irow = min(1 + min(t + tstep, ntiles - 1) * 16 + r16, N1 - 1);      // (past the end: the last tile again, never used)
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) bn[ks] = *reinterpret_cast<const uint4*>(item_emb + (size_t)irow * E + (ks * 4 + kg) * 4);
+        }
+        f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) Mma<float>::mma(ua[ks], b[ks], acc);
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) {
+            const uint64_t key = topk_key(acc[rr], i);
+            if (i < N1 && live[rr] && key > thr[rr]) {
+                const int ul = kg * 4 + rr;
+                int lo = 0, hi = nex[ul];
+                while (lo < hi) {
+                    const int mid = (lo + hi) >> 1;
+                    if (excl[ul][mid] < i) lo = mid + 1; else hi = mid;
+                }
+                if (!(lo < nex[ul] && excl[ul][lo] == i)) {
+                    const int p = atomicAdd(&cnt[ul], 1);
+                    buf[ul * cap + p] = key;
+                    if (p >= cap - STEP_KEYS) trig = s;      // (every writer of this step writes s; the next step's writers come after the barrier)
+                }
+            }
+        }
+        __syncthreads();
+        if (trig == s) {                                  // uniform: no wave can write step s + 1 before all have read it (see the note above)
+            topk_compact(buf, cap, K, cnt, thr_s);
+#pragma unroll
+            for (int rr = 0; rr < 4; ++rr) thr[rr] = thr_s[kg * 4 + rr];
+        }
+    }
+    topk_compact(buf, cap, K, cnt, thr_s);
+    for (int e = tid; e < 16 * K; e += 256) {
+        const int ul = e / K, j = e - ul * K;
+        if (u0 + ul < U) ws[((size_t)blockIdx.y * U + u0 + ul) * K + j] = buf[ul * cap + j];
+    }
+}
+
+// one item range: the workgroup's sorted list is the answer
+__global__ void topk_decode_kernel(const uint64_t* __restrict__ ws, int32_t* __restrict__ ids, float* __restrict__ scores, int64_t n) {
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256) topk_emit(ws[e], ids + e, scores + e);
+}
+
+// gy > 1 item ranges: one workgroup per user; list l of user u is ws[(l * U + u) * K ..][K], sorted descending
+__global__ void __launch_bounds__(256) topk_merge_kernel(const uint64_t* __restrict__ ws, int32_t* __restrict__ ids, float* __restrict__ scores,
+                                                         int U, int K, int gy) {
+    extern __shared__ uint64_t lists[];              // [gy][K]
+    const int u = blockIdx.x, tid = threadIdx.x, n = gy * K;
+    for (int e = tid; e < n; e += 256) {
+        const int l = e / K, j = e - l * K;
+        lists[e] = ws[((size_t)l * U + u) * K + j];
+    }
+    for (int j = tid; j < K; j += 256) topk_emit(0, ids + (size_t)u * K + j, scores + (size_t)u * K + j);    // pads; overwritten below where a key lands
+    __syncthreads();                                  // (also orders the pad stores before the stores below: one workgroup)
+    for (int e = tid; e < n; e += 256) {
+        const uint64_t x = lists[e];
+        if (x == 0) continue;
+        const int l = e / K;
+        int r = e - l * K;
+        for (int m = 0; m < gy && r < K; ++m) {
+            if (m == l) continue;
+            const uint64_t* L = lists + m * K;
+            int lo = 0, hi = K;                       // keys of list m above x: the first position holding a key <= x
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (L[mid] > x) lo = mid + 1; else hi = mid;
+            }
+            r += lo;
+        }
+        if (r < K) topk_emit(x, ids + (size_t)u * K + r, scores + (size_t)u * K + r);
+    }
+}
+
+int topk_ranges(int U, int N1) {                     // a4r_eval_rank's grid, at most MAX_RANGES item ranges
+    const int gx = (U + 15) / 16;
+    int gy = 2048 / gx; if (gy < 1) gy = 1;
+    const int ntiles = (N1 - 1 + 15) / 16;
+    if (gy > (ntiles + 3) / 4) gy = (ntiles + 3) / 4;
+    return gy < MAX_RANGES ? gy : MAX_RANGES;
+}
+
+int topk_cap(int K) {                                // candidate slots per user: a power of two >= K + one step's keys
+    int c = 128;
+    while (c < K + STEP_KEYS) c <<= 1;
+    return c;
+}
+
+template <typename Kern> int set_lds(Kern kernel, size_t bytes) {
+    if (bytes > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess)
+        return A4R_ELAUNCH;
+    return A4R_OK;
+}
+
+template <int E> int launch_partial(hipStream_t s, dim3 grid, size_t lds, const float* prec, const float* item_emb, const int32_t* excl_ptr,
+                                    const int32_t* excl_idx, uint64_t* ws, int U, int N1, int K, int cap) {
+    if (int rc = set_lds(topk_partial_kernel<E>, lds)) return rc;
+    hipLaunchKernelGGL(topk_partial_kernel<E>, grid, dim3(256), lds, s, prec, item_emb, excl_ptr, excl_idx, ws, U, N1, K, cap);
+    return A4R_OK;
+}
+
+bool topk_shape_ok(int U, int N1, int K) { return U > 0 && N1 >= 2 && K >= 1 && K <= A4R_TOPK_MAX_K; }
+
+}  // namespace
+
+extern "C" size_t a4r_topk_ws_bytes(int U, int N1, int K) {
+    if (!topk_shape_ok(U, N1, K)) return 0;
+    return (size_t)topk_ranges(U, N1) * (size_t)U * (size_t)K * sizeof(uint64_t);
+}
+
+extern "C" int a4r_topk_items(void* stream, const float* prec, const float* item_emb, const int32_t* excl_ptr, const int32_t* excl_idx,
+                              int32_t* ids, float* scores, void* ws, int U, int N1, int E, int K) {
+    if (!prec || !item_emb || !excl_ptr || !excl_idx || !ids || !scores || !ws || !topk_shape_ok(U, N1, K)) return A4R_EINVAL;
+    if (E != 64 && E != 128 && E != 256 && E != 512) return A4R_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(prec) | reinterpret_cast<uintptr_t>(item_emb)) & 15u) return A4R_EINVAL;
+    if (reinterpret_cast<uintptr_t>(ws) & 7u) return A4R_EINVAL;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    uint64_t* w = static_cast<uint64_t*>(ws);
+    const int gy = topk_ranges(U, N1), cap = topk_cap(K);
+    const dim3 grid((U + 15) / 16, gy);
+    const size_t lds = (size_t)16 * cap * sizeof(uint64_t);
+    int rc;
+    if (E == 64) rc = launch_partial<64>(s, grid, lds, prec, item_emb, excl_ptr, excl_idx, w, U, N1, K, cap);
+    else if (E == 128) rc = launch_partial<128>(s, grid, lds, prec, item_emb, excl_ptr, excl_idx, w, U, N1, K, cap);
+    else if (E == 256) rc = launch_partial<256>(s, grid, lds, prec, item_emb, excl_ptr, excl_idx, w, U, N1, K, cap);
+    else rc = launch_partial<512>(s, grid, lds, prec, item_emb, excl_ptr, excl_idx, w, U, N1, K, cap);
+    if (rc) return rc;
+    if (gy == 1) {
+        const int64_t n = (int64_t)U * K;
+        const int blocks = (int)((n + 255) / 256 < 8192 ? (n + 255) / 256 : 8192);
+        hipLaunchKernelGGL(topk_decode_kernel, dim3(blocks), dim3(256), 0, s, w, ids, scores, n);
+    } else {
+        const size_t mlds = (size_t)gy * K * sizeof(uint64_t);
+        if ((rc = set_lds(topk_merge_kernel, mlds))) return rc;
+        hipLaunchKernelGGL(topk_merge_kernel, dim3(U), dim3(256), mlds, s, w, ids, scores, U, K, gy);
+    }
+    return a4r_launch_status();
+}

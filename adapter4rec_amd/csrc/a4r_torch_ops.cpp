@@ -14,6 +14,8 @@
 //   torch.ops.a4r.score_bce_fwd / _bwd     a4r_score_bce_*        Model.forward / ModelCPC.forward head     (model/model.py:58-68,127-133)
 //   torch.ops.a4r.fused_adam_step          a4r_adam_step          optim.Adam over the flat buffers, lr groups (run.py:505-529)
 //   torch.ops.a4r.topk_rank_eval           a4r_eval_rank          eval_model's per-user rank                (data_utils/metrics.py:82-116)
+//   torch.ops.a4r.topk_items               a4r_topk_items         the K best items per user, list excluded  (data_utils/metrics.py: recommend); the one op that
+//                                                                 allocates: it returns (ids, scores) and takes its workspace from the caching allocator
 //   torch.ops.a4r.lora_bwd                 a4r_lora_bwd_fused     loralib Linear (query, value): every low-rank gradient in one pass (run_adapter.py:384-395)
 //   torch.ops.a4r.encoder_layer_fwd / _bwd a4r_encoder_layer_fwd / _bwd  one post-LN HF BertLayer + serial Houlsby wrappers per call (model/encoders.py:39-56, model/model.py:292-297)
 //   torch.ops.a4r.sasrec_block_fwd / _bwd  a4r_sasrec_block_fwd / _bwd   one adapted SASRec TransformerBlock per call (model/modules.py:45-87, model/model.py:341-376)
@@ -206,6 +208,29 @@ void topk_rank_eval(const Tensor& prec, const Tensor& item_emb, const Tensor& ta
     status(a4r_eval_rank(cur_stream(prec), prec.data_ptr<float>(), item_emb.data_ptr<float>(), target.data_ptr<int32_t>(), hist_ptr.data_ptr<int32_t>(),
                          hist_idx.data_ptr<int32_t>(), rank.data_ptr<int32_t>(), (int)U, (int)N1, (int)E),
            "a4r_eval_rank");
+}
+
+// (ids int32 [U, k], scores fp32 [U, k]) = the k best items 1 .. N1-1 of every user outside its CSR exclusion list, score descending, ties by smaller id,
+// short lists padded with id 0 / -inf (include/a4r.h: a4r_topk_items)
+std::tuple<Tensor, Tensor> topk_items(const Tensor& prec, const Tensor& item_emb, const Tensor& excl_ptr, const Tensor& excl_idx, int64_t k) {
+    TORCH_CHECK(prec.dim() == 2 && item_emb.dim() == 2 && prec.size(1) == item_emb.size(1), "a4r::topk_items: prec [U, E], item_emb [N + 1, E]");
+    const int64_t U = prec.size(0), N1 = item_emb.size(0), E = prec.size(1);
+    chk_f32(prec, "prec", prec, U * E); chk_f32(item_emb, "item_emb", prec, N1 * E);
+    for (const Tensor* t : {&excl_ptr, &excl_idx})
+        TORCH_CHECK(t->is_cuda() && t->device() == prec.device() && t->scalar_type() == at::kInt && t->is_contiguous(),
+                    "a4r::topk_items: excl_ptr / excl_idx must be contiguous int32 device tensors");
+    TORCH_CHECK(excl_ptr.numel() == U + 1, "a4r::topk_items: excl_ptr [U + 1] (CSR)");
+    TORCH_CHECK(k >= 1 && k <= A4R_TOPK_MAX_K, "a4r::topk_items: k must be in 1 .. ", A4R_TOPK_MAX_K, ", got ", k);
+    TORCH_CHECK(U >= 1 && N1 >= 2, "a4r::topk_items: U >= 1 users and N1 >= 2 table rows");
+    Tensor ids = at::empty({U, k}, prec.options().dtype(at::kInt));
+    Tensor scores = at::empty({U, k}, prec.options());
+    const size_t wsb = a4r_topk_ws_bytes((int)U, (int)N1, (int)k);
+    Tensor ws = at::empty({(int64_t)wsb}, prec.options().dtype(at::kByte));
+    Tensor idx = excl_idx.numel() ? excl_idx : at::zeros({1}, excl_idx.options());     // (an empty list has no data pointer)
+    status(a4r_topk_items(cur_stream(prec), prec.data_ptr<float>(), item_emb.data_ptr<float>(), excl_ptr.data_ptr<int32_t>(), idx.data_ptr<int32_t>(),
+                          ids.data_ptr<int32_t>(), scores.data_ptr<float>(), ws.data_ptr(), (int)U, (int)N1, (int)E, (int)k),
+           "a4r_topk_items");
+    return {ids, scores};
 }
 
 // The low-rank gradients of a block's two LoRAs (query: a, value: b) from one pass over x [M, H] and the two slices dqa, dqb [M, H] of the fused qkv
@@ -436,6 +461,7 @@ TORCH_LIBRARY(a4r, m) {
     m.def("fused_adam_step(Tensor(a!) p, Tensor g, Tensor(b!) m, Tensor(c!) v, Tensor seg_end, Tensor seg_group, Tensor group_lr, int step, float beta1=0.9, "
           "float beta2=0.999, float eps=1e-8, float grad_scale=1.0) -> ()", &fused_adam_step);
     m.def("topk_rank_eval(Tensor prec, Tensor item_emb, Tensor target, Tensor hist_ptr, Tensor hist_idx, Tensor(a!) rank) -> ()", &topk_rank_eval);
+    m.def("topk_items(Tensor prec, Tensor item_emb, Tensor excl_ptr, Tensor excl_idx, int k) -> (Tensor, Tensor)", &topk_items);
     m.def("lora_bwd(Tensor x, Tensor dqa, Tensor dqb, Tensor Aa, Tensor Ab, Tensor BTa, Tensor BTb, float scale_a, float scale_b, Tensor(a!) dAa, Tensor(b!) dAb, "
           "Tensor(c!) dBa, Tensor(d!) dBb, Tensor(e!)? dbias_a, Tensor(f!)? dbias_b, Tensor(g!) ws) -> ()", &lora_bwd);
     m.def("encoder_layer_fwd(Tensor x, Tensor[] w, Tensor[] ad1, Tensor[] ad2, Tensor[] saved, Tensor(a!) x1, Tensor(b!) x_out, Tensor? key_mask, Tensor? offsets, int n_items, int S, "

@@ -23,6 +23,8 @@ from ..inject import freeze_all
 from ..optim import FusedAdam
 from . import Model, ModelCPC, ViTForImageClassification, ViTMAEModel
 from .data_utils import eval_model, get_itemId_embeddings, get_itemLMDB_embeddings, open_image_db, read_behaviors, read_images
+from ..data_utils.metrics import write_recommendations
+from ..data_utils.preprocess import read_behavior_names
 from .image_io import Build_Lmdb_Dataset, assemble_batch, collate_host
 from .inject import inject_adapters, optimizer_groups
 from .parameters import parse_args
@@ -224,6 +226,29 @@ def test(args, use_modal, local_rank, Log_file, Log_screen, model_dir, start_tim
     run_eval_once(model, db, item_id_to_keys, hist_test, users_test, 256, item_num, 'test', local_rank, args, Log_file)
 
 
+def recommend(args, use_modal, local_rank, Log_file, Log_screen, model_dir, start_time):
+    """--mode recommend: the model test() evaluates, asked for the --topk next items after every kept user's whole known sequence (the test
+    split's input with its held-out item), everything in that sequence excluded; rank 0 writes --recommend_out."""
+    if not use_modal:
+        check_id_flags(args)
+    cv_model = load_backbone(args, Log_file) if use_modal else None
+    path = os.path.join(args.root_data_dir, args.dataset, args.behaviors)
+    before_keys, before_name2id = read_images(os.path.join(args.root_data_dir, args.dataset, args.images))
+    item_num, item_id_to_keys, _, _, users_test, _, hist_test = read_behaviors(path, before_keys, before_name2id, args.max_seq_len, args.min_seq_len, Log_file)
+    user_names, item_names = read_behavior_names(path, before_name2id, args.max_seq_len, args.min_seq_len)
+    db = open_image_db(os.path.join(args.root_data_dir, args.dataset, args.lmdb_data)) if use_modal else None
+    model, _, _ = build_model(args, item_num, use_modal, cv_model, local_rank, Log_file, model_dir)
+    model = FlatDDP(model, device_ids=[local_rank], output_device=local_rank)
+    if db is None:
+        emb = get_itemId_embeddings(model, item_num, 256, args, local_rank)
+    else:
+        emb = get_itemLMDB_embeddings(model, item_num, item_id_to_keys, 256, args, local_rank, db=db)
+    out = args.recommend_out or os.path.join(model_dir, f'recommend_{args.load_ckpt_name}.tsv')
+    out = write_recommendations(model, users_test, hist_test, emb, args.topk, 256, args, user_names, item_names, out)
+    if out:
+        Log_file.info(f'recommend: top-{args.topk} lists of {len(users_test)} users -> {out}')
+
+
 def main(argv=None):
     args = parse_args(argv)
     local_rank = args.local_rank if args.local_rank >= 0 else int(os.environ.get('LOCAL_RANK', 0))
@@ -242,7 +267,10 @@ def main(argv=None):
     Log_file.info(args)
     os.makedirs(model_dir, exist_ok=True)
     t0 = time.time()
-    (test if 'test' in args.mode else train)(args, use_modal, local_rank, Log_file, Log_screen, model_dir, t0)
+    if args.mode == 'recommend':
+        recommend(args, use_modal, local_rank, Log_file, Log_screen, model_dir, t0)
+    else:
+        (test if 'test' in args.mode else train)(args, use_modal, local_rank, Log_file, Log_screen, model_dir, t0)
 
 
 if __name__ == '__main__':

@@ -188,3 +188,104 @@ def eval_model(model, user_history, eval_seq, item_embeddings, test_batch_size, 
     mean_eval = [float(hit[:n_users].mean().item()), float(ndcg[:n_users].mean().item())]
     print_metrics(mean_eval, Log_file, v_or_t)
     return mean_eval[0]
+
+
+def _recommend_inputs(user_seqs, exclude, uids, T):
+    """recommend()'s host side for the listed users: each one's last T items left-padded into ids / log_mask [n, T] (the layout _prepare_eval_set
+    gives an evaluation input), and the exclusion lists as CSR (ptr [n + 1] int64, flat ids int32 + one spare 0)."""
+    import itertools
+    seqs = [list(user_seqs[int(u)])[-T:] for u in uids]
+    n = len(seqs)
+    lens = np.fromiter((len(s) for s in seqs), dtype=np.int64, count=n)
+    if n and int(lens.min()) == 0:
+        raise ValueError(f'user {int(uids[int(lens.argmin())])}: an empty sequence has nothing to recommend from')
+    rows = np.repeat(np.arange(n), lens)
+    cols = (np.arange(int(lens.sum())) - np.repeat(np.cumsum(lens) - lens, lens)) + np.repeat(T - lens, lens)
+    ids = np.zeros((n, T), dtype=np.int64)
+    mask = np.zeros((n, T), dtype=np.float32)
+    ids[rows, cols] = np.fromiter(itertools.chain.from_iterable(seqs), dtype=np.int64, count=int(lens.sum()))
+    mask[rows, cols] = 1.0
+    ex = [np.asarray(exclude[int(u)]).reshape(-1).astype(np.int64) for u in uids] if exclude is not None else [np.asarray(user_seqs[int(u)], dtype=np.int64).reshape(-1) for u in uids]
+    el = np.fromiter((e.size for e in ex), dtype=np.int64, count=n)
+    if n and int(el.max()) > L.EVAL_MAX_HISTORY:              # never truncate: an unexcluded item would be recommended silently
+        u = int(el.argmax())
+        raise ValueError(f'user {int(uids[u])}: exclusion list of {int(el[u])} items exceeds A4R_EVAL_MAX_HISTORY = {L.EVAL_MAX_HISTORY}')
+    ptr = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(el, out=ptr[1:])
+    flat = np.concatenate(ex + [np.zeros(1, np.int64)])
+    # ids outside int32 can never name a table row; clamp them to -1 (ignored like any id outside 1 .. N1-1) instead of letting them wrap
+    flat = np.where((flat < 0) | (flat > np.iinfo(np.int32).max), -1, flat).astype(np.int32)
+    return ids, mask, ptr, flat
+
+
+def recommend(model, user_seqs, item_embeddings, k, args, exclude=None, user_ids=None):
+    """The k best items for each listed user (default: every user of ``user_seqs``), after the user's sequence.
+
+    ``user_seqs[u]``: the user's item ids (1 .. N); its last ``max_seq_len`` items go through ``user_encoder``, left-padded as an evaluation
+    input is.  ``exclude[u]`` (default: ``user_seqs[u]``): items never returned, at most ``A4R_EVAL_MAX_HISTORY`` = 264 of them (longer lists
+    raise ``ValueError``: never truncated); ids 0 or outside the table are ignored.  ``item_embeddings``: the fp32 [N + 1, E] table of
+    ``get_item_embeddings`` / ``get_itemLMDB_embeddings`` / ``get_itemId_embeddings``.
+    Returns (ids LongTensor [U, k], scores fp32 [U, k]) on the model's device: score descending, ties by smaller id; a user with fewer than k
+    candidates gets id 0 / score -inf in the remaining slots.  One a4r_topk_items launch pair per batch of users (the [users, items] score matrix
+    is never formed)."""
+    inner = _inner(model, args)
+    dev = next(model.parameters()).device
+    emb = item_embeddings.to(dev).float().contiguous()
+    T = int(args.max_seq_len)
+    E = emb.shape[1]
+    k = int(k)
+    uids = np.arange(len(user_seqs), dtype=np.int64) if user_ids is None else np.asarray(user_ids, dtype=np.int64).reshape(-1)
+    if uids.size == 0:
+        return torch.zeros(0, k, dtype=torch.long, device=dev), torch.zeros(0, k, dtype=torch.float32, device=dev)
+    ids_np, mask_np, ptr_np, flat_np = _recommend_inputs(user_seqs, exclude, uids, T)
+    step = int(os.environ.get('A4R_EVAL_USER_BATCH', 0)) or 8192          # (eval_ranks' user batch)
+    flat = torch.from_numpy(flat_np).to(dev)
+    out_ids, out_scores = [], []
+    model.eval()
+    with torch.no_grad():
+        for a in range(0, uids.size, step):
+            b = min(a + step, uids.size)
+            nb = b - a
+            x = torch.from_numpy(ids_np[a:b]).to(dev)
+            input_embs = emb[x.reshape(-1)].view(nb, T, E)
+            prec = inner.user_encoder(input_embs, torch.from_numpy(mask_np[a:b]).to(dev), None)[:, -1].contiguous()
+            h0, h1 = int(ptr_np[a]), int(ptr_np[b])
+            ptr = torch.from_numpy((ptr_np[a:b + 1] - h0).astype(np.int32)).to(dev)
+            ids = torch.empty(nb, k, dtype=torch.int32, device=dev)
+            scores = torch.empty(nb, k, dtype=torch.float32, device=dev)
+            L.topk_items(prec, emb, ptr, flat[h0:h1 + 1], k, ids, scores)
+            out_ids.append(ids.long())
+            out_scores.append(scores)
+    return torch.cat(out_ids), torch.cat(out_scores)
+
+
+def write_recommendations(model, user_seqs, user_history, item_embeddings, k, batch_size, args, user_names, item_names, path):
+    """The runners' --mode recommend: the k next items after every user's whole known sequence (``user_seqs[u]``, the evaluation input of the
+    test split, whose last item is the held-out one), excluding ``user_history[u]`` plus that last item -- everything the user is known to have
+    seen.  Users are sharded over the data-parallel ranks as eval_model shards them; rank 0 writes ``path``: one line per user, in uid order,
+    ``user_name \\t item_1 ... item_k \\t score_1 ... score_k`` with the item file's names (pad slots of a short list omitted)."""
+    world = dist.get_world_size() if dist.is_initialized() else 1
+    rank_id = dist.get_rank() if dist.is_initialized() else 0
+    n_users = len(user_seqs)
+    uids = SequentialDistributedSampler(range(n_users), batch_size, rank=rank_id, num_replicas=world).indices()
+    exclude = {}
+    for u in uids:
+        u = int(u)
+        if u not in exclude:
+            exclude[u] = np.concatenate([np.asarray(user_history[u], dtype=np.int64).reshape(-1), np.asarray(user_seqs[u][-1:], dtype=np.int64)])
+    ids, scores = recommend(model, user_seqs, item_embeddings, k, args, exclude=exclude, user_ids=uids)
+    if world > 1:
+        parts_i = [torch.zeros_like(ids) for _ in range(world)]
+        parts_s = [torch.zeros_like(scores) for _ in range(world)]
+        dist.all_gather(parts_i, ids)
+        dist.all_gather(parts_s, scores)
+        ids, scores = torch.cat(parts_i), torch.cat(parts_s)
+    if rank_id != 0:
+        return None
+    ids, scores = ids[:n_users].cpu().numpy(), scores[:n_users].cpu().numpy()
+    with open(path, 'w') as f:
+        for u in range(n_users):
+            keep = ids[u] != 0
+            f.write(user_names[u] + '\t' + ' '.join(item_names[int(i)] for i in ids[u][keep]) + '\t'
+                    + ' '.join('%.9g' % float(s) for s in scores[u][keep]) + '\n')
+    return path

@@ -97,3 +97,23 @@ def read_behaviors(behaviors_path, before_item_id_to_dic, before_item_name_to_id
     Log_file.info('##### user seqs after clearing {}, {}, {}, {}, {}#####'.format(
         len(user_seqs), len(user_seqs), len(train), len(valid), len(test)))
     return item_num, item_id_to_dic, train, valid, test, hist_valid, hist_test
+
+
+def read_behavior_names(behaviors_path, before_item_name_to_id, max_seq_len, min_seq_len):
+    """The names read_behaviors drops (both packages' readers keep the same users and renumber the same way): user_names[uid] = the behaviours
+    file's user name of user uid, item_names[i] = the item file's name of item i (1 .. item_num; [0] = None for the pad item).  Re-derived from
+    the file: the kept users are those with >= min_seq_len items, in first-appearance order (a repeated name keeps its first place and its last
+    line, as the reader's dict does); the items occurring in their last max_seq_len + 3 entries are numbered from 1 in the item file's order."""
+    seqs, used = {}, set()
+    with open(behaviors_path, 'r') as f:
+        for line in f:
+            parts = line.strip('\n').split('\t')
+            names = parts[1].split(' ')
+            if len(names) < min_seq_len:
+                continue
+            ids = [before_item_name_to_id[x] for x in names[-(max_seq_len + 3):]]
+            seqs[parts[0]] = ids
+            used.update(ids)                   # (every kept line counts, an overwritten one too: the reader's item counts do)
+    used = sorted(used)
+    name_of = {v: k for k, v in before_item_name_to_id.items()}
+    return list(seqs.keys()), [None] + [name_of[b] for b in used]

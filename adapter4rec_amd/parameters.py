@@ -8,7 +8,7 @@ import os
 def build_parser():
     p = argparse.ArgumentParser()
     # ============== data_dir ==============
-    p.add_argument('--mode', type=str, default='train', choices=['train', 'test', 'load'])
+    p.add_argument('--mode', type=str, default='train', choices=['train', 'test', 'load', 'recommend'])
     p.add_argument('--item_tower', type=str, default='modal', choices=['modal', 'id'])
     p.add_argument('--root_data_dir', type=str, default='../')
     p.add_argument('--dataset', type=str, default='Adressa')
@@ -34,6 +34,8 @@ def build_parser():
     # ============== switch and logging setting ==============
     p.add_argument('--num_workers', type=int, default=12)
     p.add_argument('--load_ckpt_name', type=str, default='None')
+    p.add_argument('--topk', type=int, default=10)                     # --mode recommend: items per user
+    p.add_argument('--recommend_out', type=str, default=None)          # --mode recommend: output file (default <model_dir>/recommend_<load_ckpt_name>.tsv)
     p.add_argument('--label_screen', type=str, default='None')
     p.add_argument('--logging_num', type=int, default=8)
     p.add_argument('--testing_num', type=int, default=1)

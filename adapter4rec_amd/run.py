@@ -18,6 +18,8 @@ from torch.utils.data import DataLoader
 
 from .data_utils import (BuildTrainDataset, eval_model, get_doc_input_bert, get_item_embeddings, read_behaviors,
                          read_news_bert)
+from .data_utils.metrics import write_recommendations
+from .data_utils.preprocess import read_behavior_names
 from .data_utils.dataset import DeviceTrainSampler
 from .data_utils.utils import (get_checkpoint, para_and_log, report_time_eval, report_time_train, save_model, setuplogger)
 from .ddp import FlatDDP, any_rank
@@ -196,6 +198,27 @@ def test(args, use_modal, local_rank, Log_file, Log_screen, model_dir, start_tim
     run_eval_once(model, item_content, hist_test, users_test, 512, item_num, use_modal, 'test', local_rank, args, Log_file)
 
 
+def recommend_out_path(args, model_dir):
+    return args.recommend_out or os.path.join(model_dir, f'recommend_{args.load_ckpt_name}.tsv')
+
+
+def recommend(args, use_modal, local_rank, Log_file, Log_screen, model_dir, start_time):
+    """--mode recommend: the model test() evaluates, asked for the --topk next items after every kept user's whole known sequence (the test
+    split's input with its held-out item), everything in that sequence excluded; rank 0 writes --recommend_out."""
+    tokenizer, bert_model = load_backbone(args, Log_file)
+    path = os.path.join(args.root_data_dir, args.dataset, args.behaviors)
+    before_id2dic, before_name2id = read_news_bert(os.path.join(args.root_data_dir, args.dataset, args.news), args, tokenizer)
+    item_num, id2dic, _, _, users_test, _, hist_test = read_behaviors(path, before_id2dic, before_name2id, args.max_seq_len, args.min_seq_len, Log_file)
+    user_names, item_names = read_behavior_names(path, before_name2id, args.max_seq_len, args.min_seq_len)
+    item_content = np.concatenate([x for x in get_doc_input_bert(id2dic, args) if x is not None], axis=1)
+    model, _, _ = build_model(args, item_num, use_modal, bert_model, local_rank, Log_file, model_dir)
+    model = FlatDDP(model, device_ids=[local_rank], output_device=local_rank)
+    emb = get_item_embeddings(model, item_content, 512, args, use_modal, local_rank)
+    out = write_recommendations(model, users_test, hist_test, emb, args.topk, 512, args, user_names, item_names, recommend_out_path(args, model_dir))
+    if out:
+        Log_file.info(f'recommend: top-{args.topk} lists of {len(users_test)} users -> {out}')
+
+
 def setup_seed(seed):
     torch.manual_seed(seed)
     torch.cuda.manual_seed_all(seed)
@@ -219,7 +242,10 @@ def main(argv=None):
     Log_file.info(args)
     os.makedirs(model_dir, exist_ok=True)
     t0 = time.time()
-    (test if 'test' in args.mode else train)(args, use_modal, local_rank, Log_file, Log_screen, model_dir, t0)
+    if args.mode == 'recommend':
+        recommend(args, use_modal, local_rank, Log_file, Log_screen, model_dir, t0)
+    else:
+        (test if 'test' in args.mode else train)(args, use_modal, local_rank, Log_file, Log_screen, model_dir, t0)
     hours, minutes, seconds = (lambda t: (t // 3600, (t // 60) % 60, t % 60))(int(time.time() - t0))
     Log_file.info('##### (time) all: {} hours {} minutes {} seconds #####'.format(hours, minutes, seconds))
 

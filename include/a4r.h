@@ -18,6 +18,7 @@
  */
 #ifndef A4R_H
 #define A4R_H
+#include <stddef.h>
 #include <stdint.h>
 #ifdef __cplusplus
 extern "C" {
@@ -44,7 +45,7 @@ extern "C" {
 
 /* ABI version: bumped whenever a signature or struct below changes.  The Python binding (adapter4rec_amd/_lib.py) refuses a
  * library whose a4r_version() differs, so an A/B build made before a signature change cannot be called with shifted arguments. */
-#define A4R_ABI_VERSION 410
+#define A4R_ABI_VERSION 411
 int a4r_version(void);
 
 /* C[M,N] = epilogue(alpha * A[M,K] . B[N,K]^T): every nn.Linear on the path (HF BertSelfAttention
@@ -457,6 +458,22 @@ int a4r_memset_zero(void* stream, void* p, int64_t bytes);
 #define A4R_EVAL_MAX_HISTORY 264
 int a4r_eval_rank(void* stream, const float* prec, const float* item_emb, const int32_t* target,
                   const int32_t* hist_ptr, const int32_t* hist_idx, int32_t* rank, int U, int N1, int E);
+
+/* Top-K recommendation (ABI 411; data_utils/metrics.py: recommend): for user u with vector prec[u] (fp32 [U,E]) and item table item_emb (fp32 [N1,E],
+ * row 0 = pad item), the K best candidates -- items 1..N1-1 not in excl(u) -- by score(u, i) = <prec[u], item_emb[i]>, formed by the same MFMA
+ * instruction sequence as a4r_eval_rank (the bits a4r_eval_rank compares), without materialising [U,N1].
+ *   excl(u): CSR as a4r_eval_rank's history (excl_ptr [U+1], excl_idx), at most A4R_EVAL_MAX_HISTORY ids per user -- the caller checks this, longer
+ *            lists are read only up to that bound; ids 0 or >= N1 are ignored, a repeated id counts once.
+ *   ids int32 [U,K], scores fp32 [U,K]: ordered by score descending, ties by smaller item id (a total order: the result is unique and the same
+ *            bits whatever the grid).  Fewer than K candidates: the remaining slots are id 0, score -inf.  A NaN score ranks below -inf (it is
+ *            never returned ahead of a number) and is returned as the canonical quiet NaN; -0 is returned as +0.
+ *   ws: a4r_topk_ws_bytes(U, N1, K) bytes of device scratch, 8-byte aligned (each item range's K best keys per user; contents need not be kept).
+ * 1 <= K <= A4R_TOPK_MAX_K, E in {64, 128, 256, 512}, prec and item_emb 16-byte aligned, U >= 1, N1 >= 2; anything else returns A4R_EINVAL
+ * before any launch (a4r_topk_ws_bytes returns 0 for such a shape).  Two launches: per-range partial top-K, then the merge. */
+#define A4R_TOPK_MAX_K 256
+size_t a4r_topk_ws_bytes(int U, int N1, int K);
+int a4r_topk_items(void* stream, const float* prec, const float* item_emb, const int32_t* excl_ptr, const int32_t* excl_idx,
+                   int32_t* ids, float* scores, void* ws, int U, int N1, int E, int K);
 
 /* The learned item-ID table of the IDRec baseline (ABI 410; Downstream/CV/model/model.py: nn.Embedding(item_num + 1, E, padding_idx=0), fed the flat
  * slot ids of a batch).  a4r_id_index, once per step: rows[i] = ids[i] when 0 <= ids[i] <= item_num, else 0 and counted in *err (overwritten: the

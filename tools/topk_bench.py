@@ -1,0 +1,115 @@
+#!/usr/bin/env python
+"""Top-K recommendation on one MI355X: a4r_topk_items beside a4r_eval_rank (the same scoring sweep, one rank per user) and beside the torch path a
+user would otherwise write (chunked fp32 matmul, history masked, torch.topk), and recommend() end to end -- one JSON line per configuration.
+
+    python tools/topk_bench.py [--iters N] [--only NAME]
+
+Shapes: 32 768 users x 65 537 items (the evaluation benchmark's shape) and x 500 001 items (the ID tower's 500 000-item table), E = 64, K 10 / 100,
+histories of 20 uniform ids.  Kernel times are HIP-event means over N launches after a warm-up; per-kernel times: run this under
+`rocprofv3 --kernel-trace --stats -- python tools/topk_bench.py`."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+DEV = 'cuda:0'
+
+
+def timed(fn, iters):
+    fn()
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(iters):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / iters
+
+
+def data(U, N1, E, H, seed=0):
+    g = torch.Generator(device=DEV).manual_seed(seed)
+    emb = torch.randn(N1, E, device=DEV, generator=g)
+    prec = torch.randn(U, E, device=DEV, generator=g)
+    hist = torch.randint(1, N1, (U, H), device=DEV, generator=g, dtype=torch.int32)
+    ptr = (torch.arange(U + 1, device=DEV, dtype=torch.int32) * H).contiguous()
+    tgt = torch.randint(1, N1, (U,), device=DEV, generator=g, dtype=torch.int32)
+    return emb, prec, hist, ptr, tgt
+
+
+def torch_path(prec, emb, hist, k, chunk=2048):
+    """what a caller without the kernel writes: [chunk, N1] fp32 scores, pad + history masked, torch.topk"""
+    ids, scores = [], []
+    for a in range(0, prec.shape[0], chunk):
+        s = prec[a:a + chunk] @ emb.t()
+        s[:, 0] = -float('inf')
+        s.scatter_(1, hist[a:a + chunk].long(), -float('inf'))
+        v, i = torch.topk(s, k, dim=1)
+        ids.append(i)
+        scores.append(v)
+    return torch.cat(ids), torch.cat(scores)
+
+
+def kernel_cfg(name, U, N1, E, k, iters, H=20):
+    from adapter4rec_amd import _lib as L
+    emb, prec, hist, ptr, tgt = data(U, N1, E, H)
+    flat = hist.reshape(-1).contiguous()
+    ids = torch.empty(U, k, dtype=torch.int32, device=DEV)
+    sc = torch.empty(U, k, dtype=torch.float32, device=DEV)
+    rank = torch.zeros(U, dtype=torch.int32, device=DEV)
+    t_topk = timed(lambda: L.topk_items(prec, emb, ptr, flat, k, ids, sc), iters)
+    t_eval = timed(lambda: L.eval_rank(prec, emb, tgt, ptr, flat, rank), iters)
+    t_torch = timed(lambda: torch_path(prec, emb, hist, k), max(1, iters // 4))
+    ti, ts = torch_path(prec, emb, hist, k)
+    agree = float((ti.int() == ids).float().mean())                 # random fp32 data: the lists agree up to near-ties
+    return dict(name=name, users=U, items=N1, E=E, k=k, topk_ms=round(t_topk, 4), eval_rank_ms=round(t_eval, 4), torch_ms=round(t_torch, 3),
+                topk_over_eval=round(t_topk / t_eval, 3), torch_over_topk=round(t_torch / t_topk, 2), users_per_s=round(U / t_topk * 1e3),
+                id_agreement_with_torch=round(agree, 6))
+
+
+def recommend_cfg(name, U, item_num, k, iters, T=20):
+    from adapter4rec_amd.cv import Model
+    from adapter4rec_amd.cv.data_utils import get_itemId_embeddings
+    from adapter4rec_amd.data_utils.metrics import recommend
+    args = argparse.Namespace(max_seq_len=T, l2_weight=0, embedding_dim=64, num_attention_heads=2, drop_rate=0.1, transformer_block=2,
+                              CV_model_load='vit-base-patch16-224', compute_dtype='bf16', arch='sasrec', adapter_type='None')
+    model = Model(args, item_num, False, None).to(DEV)
+    emb = get_itemId_embeddings(model, item_num, 256, args, 0)
+    rng = np.random.default_rng(0)
+    seqs = {u: list(rng.integers(1, item_num + 1, size=T + 3)) for u in range(U)}
+    recommend(model, seqs, emb, k, args)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(iters):
+        ids, _ = recommend(model, seqs, emb, k, args)
+    torch.cuda.synchronize()
+    dt = (time.perf_counter() - t0) / iters
+    return dict(name=name, users=U, items=item_num + 1, E=64, k=k, recommend_ms=round(dt * 1e3, 2), users_per_s=round(U / dt))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--iters', type=int, default=20)
+    ap.add_argument('--only', default=None)
+    a = ap.parse_args()
+    cfgs = [
+        ('k10_65537', lambda: kernel_cfg('k10_65537', 32768, 65537, 64, 10, a.iters)),
+        ('k100_65537', lambda: kernel_cfg('k100_65537', 32768, 65537, 64, 100, a.iters)),
+        ('k10_500001', lambda: kernel_cfg('k10_500001', 32768, 500001, 64, 10, max(1, a.iters // 4))),
+        ('k100_500001', lambda: kernel_cfg('k100_500001', 32768, 500001, 64, 100, max(1, a.iters // 4))),
+        ('recommend_k10_65537', lambda: recommend_cfg('recommend_k10_65537', 32768, 65536, 10, 3)),
+    ]
+    for name, fn in cfgs:
+        if a.only and a.only != name:
+            continue
+        print(json.dumps(fn()), flush=True)
+
+
+if __name__ == '__main__':
+    main()
