@@ -432,7 +432,19 @@ def vit_assemble(patches, cls, pos, out, n_items, n_keep, keep_idx=None, tokens_
 
 
 def embed_bwd(ids, dpre, dword, dpos, n_items, S, roberta=False, pad_id=0):
-    require_gpu(ids, dpre)
+    """dword[id] += dpre[row], dpos[pos_id] += dpre[row] over the n_items * S token rows (include/a4r.h), padding rows skipped.  The kernel
+    indexes the tables with H = dpre.shape[1] and does not bound the ids: the shapes are checked here, before any launch.  The vocabulary
+    bound (ids < dword.shape[0]) is the caller's: checking it would read the ids back from the device."""
+    H = dpre.shape[1]
+    assert ids.dtype == torch.int64 and ids.dim() == 2 and ids.stride(1) == 1, 'ids: int64 [n_items, >= S] with unit column stride'
+    assert ids.shape[0] >= n_items and ids.shape[1] >= S, f'ids {tuple(ids.shape)} smaller than [{n_items}, {S}]'
+    assert dpre.dim() == 2 and dpre.shape[0] >= n_items * S, f'dpre {tuple(dpre.shape)}: fewer than {n_items * S} rows'
+    for name, t in (('dword', dword), ('dpos', dpos)):
+        assert t is None or (t.dtype == torch.float32 and t.dim() == 2 and t.is_contiguous() and t.shape[1] == H), \
+            f'{name}: contiguous fp32 [rows, {H}] expected, got {None if t is None else (t.dtype, tuple(t.shape), t.stride())}'
+    n_pos = S + pad_id + 1 if roberta else S         # largest pos_id + 1 (RoBERTa: cumsum(id != pad) + pad <= S + pad)
+    assert dpos is None or dpos.shape[0] >= n_pos, f'dpos has {dpos.shape[0]} rows, position ids reach {n_pos - 1}'
+    require_gpu(ids, dpre, dword, dpos)
     _check(lib().a4r_embed_bwd(_stream(), _p(ids), C.c_int(ids.stride(0)), _p(dpre), C.c_int(_ld(dpre)), _p(dword), _p(dpos),
                                C.c_int(n_items), C.c_int(S), C.c_int(dpre.shape[1]), C.c_int(int(roberta)), C.c_int(pad_id),
                                C.c_int(_dt(dpre))), 'a4r_embed_bwd')

@@ -114,7 +114,9 @@ __global__ void __launch_bounds__(256) embed_ln_kernel(const int64_t* __restrict
 }
 
 // gradient of the embedding sum: every token row of dpre is added into the rows of the word / position tables it read
-// (--fine_tune_to all, Pretraining; the reference gets this from nn.Embedding's backward).  fp32 atomics.
+// (--fine_tune_to all, Pretraining; the reference gets this from nn.Embedding's backward).  fp32 atomics.  nn.Embedding(padding_idx)
+// never gives its padding row a gradient: HF declares padding_idx = pad on the word table (BERT, RoBERTa) and on RoBERTa's position
+// table, so word row pad_id and (roberta) position row pad_id are skipped; BERT's position table has no padding row.
 template <typename T>
 __global__ void __launch_bounds__(256) embed_bwd_kernel(const int64_t* __restrict__ ids, int ld_ids, const T* __restrict__ dpre, int ldd,
                                                         float* __restrict__ dword, float* __restrict__ dpos, int n_rows, int S, int H,
@@ -131,10 +133,13 @@ __global__ void __launch_bounds__(256) embed_bwd_kernel(const int64_t* __restric
             for (int t = 0; t <= s; ++t) c += (idr[t] != pad_id && idr[t] >= 0);
             pid = (idraw != pad_id && idraw >= 0) ? c + pad_id : pad_id;
         }
+        float* const dw = (dword && id != pad_id) ? dword + (size_t)id * H : nullptr;
+        float* const dp = (dpos && !(roberta && pid == pad_id)) ? dpos + (size_t)pid * H : nullptr;
+        if (!dw && !dp) continue;                               // (wave-uniform: one wave per row)
         for (int c = lane; c < H; c += 64) {
             const float g = Elem<T>::ld(dpre + (size_t)row * ldd + c);
-            if (dword) atomicAdd(dword + (size_t)id * H + c, g);
-            if (dpos) atomicAdd(dpos + (size_t)pid * H + c, g);
+            if (dw) atomicAdd(dw + c, g);
+            if (dp) atomicAdd(dp + c, g);
         }
     }
 }

@@ -310,7 +310,11 @@ int a4r_embed_ln(void* stream, const int64_t* ids, int ld_ids, const float* word
 /* key_mask_out (optional, fp32 [n_items, S]): the attention key mask = columns S .. 2S-1 of the ids || mask rows (Bert_Encoder splits
  * them at encoders.py:48-57), converted in the same pass.  pre_out (optional, same dtype / ld as out): the embedding sum before the LayerNorm; stats_out (optional, fp32 [rows, 2]):
  * mean, rstd -- what a4r_ln_bwd needs when the embedding LayerNorm or tables are trained (--finetune_layernorm, --fine_tune_to all).
- * a4r_embed_bwd: the nn.Embedding backward: dword[id] += dpre[row], dpos[pos_id] += dpre[row] (either table may be NULL). */
+ * a4r_embed_bwd: the nn.Embedding backward: dword[id] += dpre[row], dpos[pos_id] += dpre[row] (either table may be NULL; fp32, row
+ * stride H; fp32 atomics, so the order of the sums is not fixed).  As nn.Embedding(padding_idx) as HF declares it: word row pad_id gets
+ * no gradient (BERT and RoBERTa), RoBERTa's position row pad_id none either (pads and negative ids); BERT's positions have no padding
+ * row.  A negative id -(r + 1) adds into word row r (skipped only when r == pad_id).  Ids must lie inside dword, pos_ids inside dpos: the kernel does
+ * not check (adapter4rec_amd/_lib.py:embed_bwd checks the table shapes on the host). */
 int a4r_embed_bwd(void* stream, const int64_t* ids, int ld_ids, const void* dpre, int ldd, float* dword, float* dpos,
                   int n_items, int S, int H, int roberta, int pad_id, int dtype);
 

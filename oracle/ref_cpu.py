@@ -140,15 +140,24 @@ def position_ids(ids, cfg):
     return torch.arange(s).unsqueeze(0).expand(n, s)
 
 
+def embedding(table, idx, padding_idx=None):
+    """nn.Embedding(padding_idx): table[idx], where the rows read at padding_idx pass no gradient back to the table."""
+    if padding_idx is None:
+        return table[idx]
+    return torch.where((idx == padding_idx).unsqueeze(-1), table.detach()[idx], table[idx])
+
+
 def bert_embed(sd, ids, cfg):
     e = BERT + 'embeddings.'
+    pad = cfg['pad_token_id']                               # HF: word_embeddings.padding_idx = pad (BERT, RoBERTa); position_embeddings
+    pos_pad = pad if cfg['encoder'] == 'roberta' else None  # .padding_idx = pad for RoBERTa only
     if e + 'word_embeddings.learned_embedding' in sd:      # soft prompt, model/model.py:586-630 SoftEmbedding: the first n_tokens
         le = sd[e + 'word_embeddings.learned_embedding']    # word vectors of every title are REPLACED by the learned rows
         n = le.shape[0]
-        w = torch.cat([le.unsqueeze(0).expand(ids.shape[0], -1, -1), sd[e + 'word_embeddings.wte.weight'][ids[:, n:]]], 1)
+        w = torch.cat([le.unsqueeze(0).expand(ids.shape[0], -1, -1), embedding(sd[e + 'word_embeddings.wte.weight'], ids[:, n:], pad)], 1)
     else:
-        w = sd[e + 'word_embeddings.weight'][ids]
-    x = w + sd[e + 'position_embeddings.weight'][position_ids(ids, cfg)] \
+        w = embedding(sd[e + 'word_embeddings.weight'], ids, pad)
+    x = w + embedding(sd[e + 'position_embeddings.weight'], position_ids(ids, cfg), pos_pad) \
         + sd[e + 'token_type_embeddings.weight'][0]
     x = layer_norm(x, sd[e + 'LayerNorm.weight'], sd[e + 'LayerNorm.bias'], cfg['bert_ln_eps'])
     return _drop(cfg, 'rows', 999, x, 'p_hidden')          # HF BertEmbeddings.forward: LayerNorm -> dropout

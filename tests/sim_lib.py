@@ -379,20 +379,25 @@ def vit_assemble(patches, cls, pos, out, n_items, n_keep, keep_idx=None, tokens_
 
 
 def _pos_ids(ids, n_items, S, roberta, pad_id):
-    idv = ids[:, :S]
+    """(word rows, position ids): a negative id -(r + 1) reads word row r and counts as a pad for RoBERTa's positions."""
+    raw = ids[:n_items, :S]
+    idv = torch.where(raw < 0, -raw - 1, raw)
     if roberta:
-        m = (idv != pad_id).long()
+        m = ((raw != pad_id) & (raw >= 0)).long()
         return idv, torch.cumsum(m, 1) * m + pad_id
     return idv, torch.arange(S).expand(n_items, S)
 
 
 def embed_bwd(ids, dpre, dword, dpos, n_items, S, roberta=False, pad_id=0):
+    """nn.Embedding(padding_idx) backward: word row pad_id gets nothing, nor RoBERTa's position row pad_id."""
     idv, pid = _pos_ids(ids, n_items, S, roberta, pad_id)
     g = dpre[:n_items * S].float()
     if dword is not None:
-        dword.index_add_(0, idv.reshape(-1), g)
+        w = idv.reshape(-1) != pad_id
+        dword.index_add_(0, idv.reshape(-1)[w], g[w])
     if dpos is not None:
-        dpos.index_add_(0, pid.reshape(-1), g)
+        p = pid.reshape(-1) != pad_id if roberta else torch.ones(n_items * S, dtype=torch.bool)
+        dpos.index_add_(0, pid.reshape(-1)[p], g[p])
 
 
 def embed_ln(ids, word, pos, type0, gamma, beta, eps, out, n_items, S, roberta=False, pad_id=0,
