@@ -5,6 +5,7 @@ raises -- there is no PyTorch / CPU fallback.  Tensors are passed as raw device 
 leading dimensions; kernels are enqueued on torch's current HIP stream.
 """
 import ctypes as C
+import math
 import os
 
 import torch
@@ -28,11 +29,12 @@ EXPORTS = [
     'a4r_eval_rank', 'a4r_dropout_apply', 'a4r_gemm_variant', 'a4r_gemm_tail_plan', 'a4r_gemm_tail_max', 'a4r_gemm_rows_256', 'a4r_adapter_ln_fwd', 'a4r_adapter_ln_bwd', 'a4r_ln_fwd_fp8', 'a4r_ln_fwd_sum', 'a4r_quant_rows_fp8', 'a4r_lora_merge', 'a4r_lora_merge_batch', 'a4r_lora_bwd_fused', 'a4r_lora_bwd_fused_ws_floats', 'a4r_phm_build', 'a4r_phm_bwd', 'a4r_unpack_add', 'a4r_memset_zero',
     'a4r_sasrec_block_fwd', 'a4r_sasrec_block_bwd', 'a4r_scatter_rows_fill', 'a4r_attn_long_fwd', 'a4r_attn_long_bwd', 'a4r_patchify', 'a4r_vit_assemble', 'a4r_resample_u8', 'a4r_embed_bwd', 'a4r_mae_keep_indices',
     'a4r_encoder_layer_fwd', 'a4r_encoder_layer_bwd', 'a4r_id_index', 'a4r_id_index_ws_ints', 'a4r_id_grad_sum',
-    'a4r_topk_items',
+    'a4r_topk_items', 'a4r_grad_sumsq', 'a4r_adamw_step',
 ]
 ID_SUM_CHUNK = 16          # A4R_ID_SUM_CHUNK (include/a4r.h)
 TOPK_MAX_K = 256           # A4R_TOPK_MAX_K (include/a4r.h)
 TOPK_E = (64, 128, 256, 512)
+GRAD_NORM_PARTS = 1024     # A4R_GRAD_NORM_PARTS (include/a4r.h)
 
 
 class GemmArgs(C.Structure):
@@ -694,6 +696,53 @@ def adam_step(p, g, m, v, seg_end, seg_group, group_lr, step, beta1=0.9, beta2=0
     _check(lib().a4r_adam_step(_stream(), _p(p), _p(g), _p(m), _p(v), C.c_int64(p.numel()), _p(seg_end), _p(seg_group),
                                C.c_int(seg_end.numel()), _p(group_lr), C.c_int(step), C.c_float(beta1), C.c_float(beta2),
                                C.c_float(eps), C.c_float(grad_scale)), 'a4r_adam_step')
+
+
+def _need(cond, what):
+    if not cond:
+        raise ValueError(what)
+
+
+def grad_sumsq(g, partials, grad_scale=1.0):
+    """a4r_grad_sumsq: partials (fp64 [GRAD_NORM_PARTS]) = the fixed-order fp64 partial sums of (g * grad_scale)^2 that a4r_adamw_step clips
+    with.  g is read with 16-byte loads when it is 16-byte aligned; the partials do not depend on that."""
+    _need(g.dtype == torch.float32 and g.is_contiguous() and g.numel() > 0, 'grad_sumsq: g must be a non-empty contiguous fp32 tensor')
+    _need(partials.dtype == torch.float64 and partials.is_contiguous() and partials.numel() == GRAD_NORM_PARTS,
+          f'grad_sumsq: partials must be contiguous fp64 with {GRAD_NORM_PARTS} elements')
+    require_gpu(g, partials)
+    _check(lib().a4r_grad_sumsq(_stream(), _p(g), C.c_int64(g.numel()), C.c_float(grad_scale), _p(partials)), 'a4r_grad_sumsq')
+
+
+def adamw_step(p, g, m, v, seg_end, seg_group, group_lr, group_wd, step, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=1.0, decoupled=True,
+               partials=None, max_norm=0.0, norm_out=None):
+    """a4r_adamw_step: Adam with per-group weight decay group_wd (decoupled: AdamW, else torch Adam's coupled form) and, when partials (grad_sumsq of
+    this g) is given, the gradient clipped to max_norm with the pre-clip norm stored into norm_out (a one-element fp32 tensor, optional).  The quad
+    kernel runs when n >= 2^20 and p, g, m, v are 16-byte aligned; the results are the same either way.  Argument errors raise ValueError before
+    the call."""
+    n = p.numel()
+    for name, t in (('p', p), ('g', g), ('m', m), ('v', v)):
+        _need(t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n and n > 0,
+              f'adamw_step: {name} must be a contiguous fp32 tensor of p\'s {n} (> 0) elements')
+    for name, t in (('seg_end', seg_end), ('seg_group', seg_group)):
+        _need(t.dtype == torch.int32 and t.is_contiguous(), f'adamw_step: {name} must be contiguous int32')
+    _need(seg_end.numel() == seg_group.numel() > 0, 'adamw_step: seg_end and seg_group must hold the same number (> 0) of segments')
+    for name, t in (('group_lr', group_lr), ('group_wd', group_wd)):
+        _need(t.dtype == torch.float32 and t.is_contiguous(), f'adamw_step: {name} must be contiguous fp32')
+    _need(group_lr.numel() == group_wd.numel(), 'adamw_step: group_lr and group_wd must hold one value per group')
+    _need(int(step) >= 1, 'adamw_step: step counts from 1')
+    if partials is not None:
+        _need(partials.dtype == torch.float64 and partials.is_contiguous() and partials.numel() == GRAD_NORM_PARTS,
+              f'adamw_step: partials must be contiguous fp64 with {GRAD_NORM_PARTS} elements')
+        _need(math.isfinite(max_norm) and max_norm > 0, f'adamw_step: max_norm must be a finite positive number, got {max_norm}')
+    if norm_out is not None:
+        _need(partials is not None, 'adamw_step: norm_out needs partials (the norm exists only when clipping)')
+        _need(norm_out.dtype == torch.float32 and norm_out.numel() == 1, 'adamw_step: norm_out must be a one-element fp32 tensor')
+    require_gpu(p, g, m, v, seg_end, seg_group, group_lr, group_wd, partials, norm_out)
+    _check(lib().a4r_adamw_step(_stream(), _p(p), _p(g), _p(m), _p(v), C.c_int64(n), _p(seg_end), _p(seg_group), C.c_int(seg_end.numel()),
+                                _p(group_lr), C.c_int(int(step)), C.c_float(beta1), C.c_float(beta2), C.c_float(eps), C.c_float(grad_scale),
+                                _p(group_wd), C.c_int(int(bool(decoupled))), _p(partials), C.c_float(max_norm if partials is not None else 0.0),
+                                _p(norm_out)),
+           'a4r_adamw_step')
 
 
 def pack_matrices(flat, desc_dev, n_desc, max_elems, dtype):

@@ -1,7 +1,8 @@
-// Scoring head + BCE loss (model/model.py:53-68, ModelCPC :118-133), Adam, parameter re-packing.
+// Scoring head + BCE loss (model/model.py:53-68, ModelCPC :118-133), Adam / AdamW with gradient-norm clipping, parameter re-packing.
 // All fp32; these are tiny, launch-latency-bound kernels.
 #include "a4r_common.h"
 #include "../../include/a4r.h"
+#include <cfloat>
 
 namespace {
 
@@ -91,12 +92,22 @@ __global__ void __launch_bounds__(256) take_inputs_kernel(const float* __restric
     }
 }
 
-// ------------------------------------------------------------------ Adam over a flat buffer
+// ------------------------------------------------------------------ Adam / AdamW over a flat buffer
+// Decay modes of the update (a4r_adamw_step's `decoupled`): none (a4r_adam_step), coupled (torch Adam(weight_decay): g += wd * p), decoupled (AdamW).
+enum { DECAY_NONE = 0, DECAY_COUPLED = 1, DECAY_DECOUPLED = 2 };
+
 // One Adam update (torch.optim.Adam: p -= (lr / bc1) * m / (sqrt(v) / sqrt(bc2) + eps)), shared by the scalar and the four-per-lane kernel; no
 // fused multiply-adds, so that both kernels round every product the same way (they must agree bit for bit: tests/test_kernels_gpu.py).
-A4R_DEV void adam_one(float& p, float g, float& m, float& v, float lr, float bc1, float bc2_sqrt, float beta1, float beta2, float eps, float grad_scale) {
+// CLIP: the gradient is multiplied by coef after grad_scale (clip_grad_norm_ before the step); the decay follows, as in torch's Adam / AdamW.
+// The DECAY_NONE, !CLIP instance is the a4r_adam_step update of earlier versions, operation for operation.
+template <int DECAY, bool CLIP>
+A4R_DEV void adam_one(float& p, float g, float& m, float& v, float lr, float wd, float coef, float bc1, float bc2_sqrt, float beta1, float beta2,
+                      float eps, float grad_scale) {
 #pragma clang fp contract(off)
-    const float gi = g * grad_scale;
+    float gi = g * grad_scale;
+    if (CLIP) gi = gi * coef;
+    if (DECAY == DECAY_COUPLED) gi = gi + wd * p;
+    if (DECAY == DECAY_DECOUPLED) p = p * (1.f - lr * wd);
     const float mi = beta1 * m + (1.f - beta1) * gi;
     const float vi = beta2 * v + (1.f - beta2) * gi * gi;
     m = mi;
@@ -104,19 +115,48 @@ A4R_DEV void adam_one(float& p, float g, float& m, float& v, float lr, float bc1
     p -= (lr / bc1) * mi / (sqrtf(vi) / bc2_sqrt + eps);
 }
 
+// The launch-boundary reduce of a4r_grad_sumsq's partials: every block sums the A4R_GRAD_NORM_PARTS fp64 partials in the same fixed order (thread t
+// adds t, t + 256, t + 512, t + 768 in turn; a fixed xor tree over the wave; the four waves in order), so every block of every launch gets the same
+// bits.  norm = sqrt(sum) in fp64, rounded once to fp32; coef = min(1, max_norm / (norm + 1e-6)) in fp32 (torch.nn.utils.clip_grad_norm_), NaN
+// when the norm is NaN, 0 when it is infinite.  Block 0 stores the norm (norm_out may be NULL).
+static_assert(A4R_GRAD_NORM_PARTS == 4 * 256, "clip_coef reads four partials per thread of a 256-thread block");
+__device__ float clip_coef(const double* __restrict__ partials, float max_norm, float* __restrict__ norm_out) {
+    __shared__ double wsum[4];
+    const int t = threadIdx.x;
+    double s = partials[t];
+    s += partials[t + 256];
+    s += partials[t + 512];
+    s += partials[t + 768];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    if ((t & 63) == 0) wsum[t >> 6] = s;
+    __syncthreads();
+    const double tot = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+    const float norm = (float)sqrt(tot);
+    if (blockIdx.x == 0 && t == 0 && norm_out) *norm_out = norm;
+    const float c = max_norm / (norm + 1e-6f);
+    return c > 1.f ? 1.f : c;                  // (a NaN c stays NaN)
+}
+
+template <int DECAY, bool CLIP>
 __global__ void __launch_bounds__(256) adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                    float* __restrict__ v, int64_t n, const int32_t* __restrict__ seg_end,
                                                    const int32_t* __restrict__ seg_group, int n_seg, const float* __restrict__ group_lr,
-                                                   float bc1, float bc2_sqrt, float beta1, float beta2, float eps, float grad_scale, int64_t base) {
+                                                   const float* __restrict__ group_wd, const double* __restrict__ partials, float max_norm,
+                                                   float* __restrict__ norm_out, float bc1, float bc2_sqrt, float beta1, float beta2, float eps,
+                                                   float grad_scale, int64_t base) {
+    const float coef = CLIP ? clip_coef(partials, max_norm, norm_out) : 1.f;
     for (int64_t i = base + (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
         int lo = 0, hi = n_seg - 1;            // first segment with seg_end > i
         while (lo < hi) {
             const int mid = (lo + hi) >> 1;
             if (seg_end[mid] > i) hi = mid; else lo = mid + 1;
         }
-        const float lr = group_lr[seg_group[lo]];
+        const int grp = seg_group[lo];
+        const float lr = group_lr[grp];
+        const float wd = DECAY != DECAY_NONE ? group_wd[grp] : 0.f;
         float pi = p[i], mi = m[i], vi = v[i];
-        adam_one(pi, g[i], mi, vi, lr, bc1, bc2_sqrt, beta1, beta2, eps, grad_scale);
+        adam_one<DECAY, CLIP>(pi, g[i], mi, vi, lr, wd, coef, bc1, bc2_sqrt, beta1, beta2, eps, grad_scale);
         m[i] = mi;
         v[i] = vi;
         p[i] = pi;
@@ -124,12 +164,16 @@ __global__ void __launch_bounds__(256) adam_kernel(float* __restrict__ p, const 
 }
 
 // Four parameters per lane and trip (16-byte accesses): full fine-tuning steps ~110 M parameters -- 3.1 GB of state per step; the scalar form
-// above moved it at 2.5 TB/s (1.2 ms).  Same arithmetic per element, so the results are bit-identical.  The segment (-> lr group) is looked up once
-// per quad and per element only where a quad straddles a segment boundary.
+// above moved it at 2.5 TB/s (1.2 ms).  Same arithmetic per element, so the results are bit-identical.  The segment (-> lr / wd group) is looked up
+// once per quad and per element only where a quad straddles a segment boundary.
+template <int DECAY, bool CLIP>
 __global__ void __launch_bounds__(256) adam4_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                     float* __restrict__ v, int64_t n4, const int32_t* __restrict__ seg_end,
                                                     const int32_t* __restrict__ seg_group, int n_seg, const float* __restrict__ group_lr,
-                                                    float bc1, float bc2_sqrt, float beta1, float beta2, float eps, float grad_scale) {
+                                                    const float* __restrict__ group_wd, const double* __restrict__ partials, float max_norm,
+                                                    float* __restrict__ norm_out, float bc1, float bc2_sqrt, float beta1, float beta2, float eps,
+                                                    float grad_scale) {
+    const float coef = CLIP ? clip_coef(partials, max_norm, norm_out) : 1.f;
     for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < n4; q += (int64_t)gridDim.x * 256) {
         const int64_t i = q * 4;
         int lo = 0, hi = n_seg - 1;            // first segment with seg_end > i
@@ -137,22 +181,69 @@ __global__ void __launch_bounds__(256) adam4_kernel(float* __restrict__ p, const
             const int mid = (lo + hi) >> 1;
             if (seg_end[mid] > i) hi = mid; else lo = mid + 1;
         }
-        float lr[4];
+        float lr[4], wd[4];
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             while (lo < n_seg - 1 && seg_end[lo] <= i + e) ++lo;
-            lr[e] = group_lr[seg_group[lo]];
+            const int grp = seg_group[lo];
+            lr[e] = group_lr[grp];
+            wd[e] = DECAY != DECAY_NONE ? group_wd[grp] : 0.f;
         }
         const float4 g4 = reinterpret_cast<const float4*>(g)[q];
         float4 m4 = reinterpret_cast<float4*>(m)[q], v4 = reinterpret_cast<float4*>(v)[q], p4 = reinterpret_cast<float4*>(p)[q];
         const float gs[4] = {g4.x, g4.y, g4.z, g4.w};
         float ms[4] = {m4.x, m4.y, m4.z, m4.w}, vs[4] = {v4.x, v4.y, v4.z, v4.w}, ps[4] = {p4.x, p4.y, p4.z, p4.w};
 #pragma unroll
-        for (int e = 0; e < 4; ++e) adam_one(ps[e], gs[e], ms[e], vs[e], lr[e], bc1, bc2_sqrt, beta1, beta2, eps, grad_scale);
+        for (int e = 0; e < 4; ++e)
+            adam_one<DECAY, CLIP>(ps[e], gs[e], ms[e], vs[e], lr[e], wd[e], coef, bc1, bc2_sqrt, beta1, beta2, eps, grad_scale);
         reinterpret_cast<float4*>(m)[q] = make_float4(ms[0], ms[1], ms[2], ms[3]);
         reinterpret_cast<float4*>(v)[q] = make_float4(vs[0], vs[1], vs[2], vs[3]);
         reinterpret_cast<float4*>(p)[q] = make_float4(ps[0], ps[1], ps[2], ps[3]);
     }
+}
+
+// Sum of squares of (g * grad_scale) for gradient clipping: A4R_GRAD_NORM_PARTS blocks, whatever n; block b writes partials[b].  The element order is
+// fixed by n alone: thread t of the grid (T threads) owns quads t, t + T, t + 2T, ... of the buffer (quad q = elements 4q .. 4q + 3, the last one
+// possibly short), each element rounded to fp32 after grad_scale, squared exactly in fp64 and added in that order; then a fixed xor tree over the
+// wave and the four waves in order.  QUAD reads whole quads with 16-byte loads (g 16-byte aligned), else element by element: the same sums.
+template <bool QUAD>
+__global__ void __launch_bounds__(256) grad_sumsq_kernel(const float* __restrict__ g, int64_t n, float grad_scale, double* __restrict__ partials) {
+    __shared__ double wsum[4];
+    const int64_t T = (int64_t)A4R_GRAD_NORM_PARTS * 256;
+    const int64_t nq = (n + 3) / 4;
+    double s = 0.0;
+    auto add = [&](float x) {
+        const double d = (double)(x * grad_scale);
+        s += d * d;
+    };
+    auto quad = [&](int64_t q) {
+        if (QUAD && q * 4 + 3 < n) {
+            const float4 g4 = reinterpret_cast<const float4*>(g)[q];
+            add(g4.x); add(g4.y); add(g4.z); add(g4.w);
+        } else {
+            for (int64_t i = q * 4; i < q * 4 + 4 && i < n; ++i) add(g[i]);
+        }
+    };
+    const int64_t n4 = n / 4;                  // whole quads
+    int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    for (; q + 3 * T < n4; q += 4 * T) {       // four whole quads in flight per lane; summed in the same order as one at a time
+        if (QUAD) {
+            float4 r[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) r[k] = reinterpret_cast<const float4*>(g)[q + k * T];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) { add(r[k].x); add(r[k].y); add(r[k].z); add(r[k].w); }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) quad(q + k * T);
+        }
+    }
+    for (; q < nq; q += T) quad(q);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) partials[blockIdx.x] = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
 }
 
 struct PackDesc {   // mirrors a4r_pack_desc_t
@@ -267,28 +358,65 @@ extern "C" int a4r_take_inputs(void* stream, const float* emb, float* out, int l
     return a4r_launch_status();
 }
 
-extern "C" int a4r_adam_step(void* stream, float* p, const float* g, float* m, float* v, int64_t n,
-                             const int32_t* seg_end, const int32_t* seg_group, int n_seg,
-                             const float* group_lr, int step, float beta1, float beta2, float eps, float grad_scale) {
-    if (!p || !g || !m || !v || !seg_end || !seg_group || !group_lr || n <= 0 || n_seg <= 0 || step < 1) return A4R_EINVAL;
+namespace {
+// Quads through adam4_kernel when the buffers are large and 16-byte aligned, the last n % 4 elements (or everything) through the scalar kernel.
+template <int DECAY, bool CLIP>
+int adam_launch(hipStream_t s, float* p, const float* g, float* m, float* v, int64_t n, const int32_t* seg_end, const int32_t* seg_group, int n_seg,
+                const float* group_lr, const float* group_wd, const double* partials, float max_norm, float* norm_out, int step, float beta1,
+                float beta2, float eps, float grad_scale) {
     const float bc1 = 1.f - powf(beta1, (float)step);
     const float bc2 = 1.f - powf(beta2, (float)step);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     int64_t n4 = 0;
     if (n >= (1 << 20) && ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) | reinterpret_cast<uintptr_t>(v)) & 15u) == 0) {
-        n4 = n / 4;                                            // quads through adam4_kernel, the last n % 4 elements through the scalar kernel
+        n4 = n / 4;
         int grid4 = (int)((n4 + 255) / 256); if (grid4 > 2048) grid4 = 2048;
-        hipLaunchKernelGGL(adam4_kernel, dim3(grid4), dim3(256), 0, s, p, g, m, v, n4, seg_end, seg_group, n_seg, group_lr, bc1, sqrtf(bc2), beta1, beta2,
-                           eps, grad_scale);
+        hipLaunchKernelGGL((adam4_kernel<DECAY, CLIP>), dim3(grid4), dim3(256), 0, s, p, g, m, v, n4, seg_end, seg_group, n_seg, group_lr, group_wd,
+                           partials, max_norm, norm_out, bc1, sqrtf(bc2), beta1, beta2, eps, grad_scale);
         if (n4 * 4 == n) return a4r_launch_status();
+        norm_out = nullptr;                                    // (stored once, by the quad launch)
     }
     // (the scalar kernel indexes from 0: hand it the tail through offset pointers and an offset-free segment search -- seg_end is absolute, so the
     // tail keeps absolute indices by starting the grid-stride loop at n4 * 4: done with a base argument)
     const int64_t base = n4 * 4;
     int grid = (int)((n - base + 255) / 256); if (grid > 2048) grid = 2048;
-    hipLaunchKernelGGL(adam_kernel, dim3(grid), dim3(256), 0, s, p, g, m, v, n, seg_end, seg_group,
-                       n_seg, group_lr, bc1, sqrtf(bc2), beta1, beta2, eps, grad_scale, base);
+    hipLaunchKernelGGL((adam_kernel<DECAY, CLIP>), dim3(grid), dim3(256), 0, s, p, g, m, v, n, seg_end, seg_group, n_seg, group_lr, group_wd,
+                       partials, max_norm, norm_out, bc1, sqrtf(bc2), beta1, beta2, eps, grad_scale, base);
     return a4r_launch_status();
+}
+}  // namespace
+
+extern "C" int a4r_adam_step(void* stream, float* p, const float* g, float* m, float* v, int64_t n,
+                             const int32_t* seg_end, const int32_t* seg_group, int n_seg,
+                             const float* group_lr, int step, float beta1, float beta2, float eps, float grad_scale) {
+    if (!p || !g || !m || !v || !seg_end || !seg_group || !group_lr || n <= 0 || n_seg <= 0 || step < 1) return A4R_EINVAL;
+    return adam_launch<DECAY_NONE, false>(reinterpret_cast<hipStream_t>(stream), p, g, m, v, n, seg_end, seg_group, n_seg, group_lr, nullptr, nullptr,
+                                          0.f, nullptr, step, beta1, beta2, eps, grad_scale);
+}
+
+extern "C" int a4r_grad_sumsq(void* stream, const float* g, int64_t n, float grad_scale, double* partials) {
+    if (!g || !partials || n <= 0) return A4R_EINVAL;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if ((reinterpret_cast<uintptr_t>(g) & 15u) == 0)
+        hipLaunchKernelGGL(grad_sumsq_kernel<true>, dim3(A4R_GRAD_NORM_PARTS), dim3(256), 0, s, g, n, grad_scale, partials);
+    else
+        hipLaunchKernelGGL(grad_sumsq_kernel<false>, dim3(A4R_GRAD_NORM_PARTS), dim3(256), 0, s, g, n, grad_scale, partials);
+    return a4r_launch_status();
+}
+
+extern "C" int a4r_adamw_step(void* stream, float* p, const float* g, float* m, float* v, int64_t n,
+                              const int32_t* seg_end, const int32_t* seg_group, int n_seg,
+                              const float* group_lr, int step, float beta1, float beta2, float eps, float grad_scale,
+                              const float* group_wd, int decoupled, const double* partials, float max_norm, float* norm_out) {
+    if (!p || !g || !m || !v || !seg_end || !seg_group || !group_lr || !group_wd || n <= 0 || n_seg <= 0 || step < 1) return A4R_EINVAL;
+    if (decoupled != 0 && decoupled != 1) return A4R_EINVAL;
+    if (partials && !(max_norm > 0.f && max_norm <= FLT_MAX)) return A4R_EINVAL;     // (NaN fails the first test)
+    if (!partials && norm_out) return A4R_EINVAL;                                     // the norm exists only when clipping
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+#define A4R_ADAMW(D, C) adam_launch<D, C>(s, p, g, m, v, n, seg_end, seg_group, n_seg, group_lr, group_wd, partials, max_norm, norm_out, step, beta1, \
+                                          beta2, eps, grad_scale)
+    if (decoupled) return partials ? A4R_ADAMW(DECAY_DECOUPLED, true) : A4R_ADAMW(DECAY_DECOUPLED, false);
+    return partials ? A4R_ADAMW(DECAY_COUPLED, true) : A4R_ADAMW(DECAY_COUPLED, false);
+#undef A4R_ADAMW
 }
 
 extern "C" int a4r_pack_matrices(void* stream, const float* flat, const a4r_pack_desc_t* desc_dev, int n_desc, int max_elems, int dtype) {

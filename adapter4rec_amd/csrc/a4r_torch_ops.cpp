@@ -13,6 +13,8 @@
 //   torch.ops.a4r.ln_fwd                   a4r_ln_fwd             LayerNorm (+ position add, dropout)       (HF BertSelfOutput / modules.py:57-66)
 //   torch.ops.a4r.score_bce_fwd / _bwd     a4r_score_bce_*        Model.forward / ModelCPC.forward head     (model/model.py:58-68,127-133)
 //   torch.ops.a4r.fused_adam_step          a4r_adam_step          optim.Adam over the flat buffers, lr groups (run.py:505-529)
+//   torch.ops.a4r.fused_adamw_step         a4r_adamw_step         Adam / AdamW with per-group weight decay; given a partials workspace it first runs
+//                                                                 a4r_grad_sumsq and clips to max_norm (clip_grad_norm_ + the step, no host read)
 //   torch.ops.a4r.topk_rank_eval           a4r_eval_rank          eval_model's per-user rank                (data_utils/metrics.py:82-116)
 //   torch.ops.a4r.topk_items               a4r_topk_items         the K best items per user, list excluded  (data_utils/metrics.py: recommend); the one op that
 //                                                                 allocates: it returns (ids, scores) and takes its workspace from the caching allocator
@@ -29,6 +31,8 @@
 #include <ATen/ATen.h>
 #include <c10/hip/HIPStream.h>
 #include <torch/library.h>
+
+#include <cmath>
 
 #include "../../include/a4r.h"
 
@@ -195,6 +199,37 @@ void fused_adam_step(Tensor p, const Tensor& g, Tensor m, Tensor v, const Tensor
                          seg_group.data_ptr<int32_t>(), (int)seg_end.numel(), group_lr.data_ptr<float>(), (int)step, (float)beta1, (float)beta2, (float)eps,
                          (float)grad_scale),
            "a4r_adam_step");
+}
+
+// fused_adam_step with per-group weight decay group_wd (decoupled: AdamW, else Adam's coupled form); with `partials` (fp64 [A4R_GRAD_NORM_PARTS], caller-owned
+// workspace) the gradient is clipped to max_norm: a4r_grad_sumsq, then a4r_adamw_step, which stores the pre-clip norm into norm_out when given
+void fused_adamw_step(Tensor p, const Tensor& g, Tensor m, Tensor v, const Tensor& seg_end, const Tensor& seg_group, const Tensor& group_lr,
+                      const Tensor& group_wd, int64_t step, double beta1, double beta2, double eps, double grad_scale, bool decoupled,
+                      const optional<Tensor>& partials, double max_norm, const optional<Tensor>& norm_out) {
+    const int64_t n = p.numel();
+    chk_f32(p, "p", p, n); chk_f32(g, "g", p, n); chk_f32(m, "m", p, n); chk_f32(v, "v", p, n);
+    TORCH_CHECK(seg_end.is_cuda() && seg_end.scalar_type() == at::kInt && seg_end.is_contiguous() && seg_group.is_cuda() && seg_group.scalar_type() == at::kInt &&
+                    seg_group.is_contiguous() && seg_group.numel() == seg_end.numel(),
+                "a4r::fused_adamw_step: seg_end / seg_group must be contiguous int32 device tensors of equal length");
+    chk_f32(group_lr, "group_lr", p, 1);
+    chk_f32(group_wd, "group_wd", p, group_lr.numel());
+    TORCH_CHECK(step >= 1, "a4r::fused_adamw_step: step counts from 1");
+    const bool clip = partials.has_value() && partials->defined();
+    if (clip) {
+        TORCH_CHECK(partials->is_cuda() && partials->device() == p.device() && partials->scalar_type() == at::kDouble && partials->is_contiguous() &&
+                        partials->numel() == A4R_GRAD_NORM_PARTS,
+                    "a4r::fused_adamw_step: partials must be a contiguous fp64 device tensor of ", A4R_GRAD_NORM_PARTS, " elements");
+        TORCH_CHECK(max_norm > 0 && std::isfinite(max_norm), "a4r::fused_adamw_step: max_norm must be a finite positive number");
+    }
+    TORCH_CHECK(clip || !(norm_out.has_value() && norm_out->defined()), "a4r::fused_adamw_step: norm_out needs partials (the norm exists only when clipping)");
+    chk_f32_vec(norm_out, "norm_out", p, 1);
+    void* s = cur_stream(p);
+    if (clip) status(a4r_grad_sumsq(s, g.data_ptr<float>(), n, (float)grad_scale, partials->data_ptr<double>()), "a4r_grad_sumsq");
+    status(a4r_adamw_step(s, p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(), n, seg_end.data_ptr<int32_t>(),
+                          seg_group.data_ptr<int32_t>(), (int)seg_end.numel(), group_lr.data_ptr<float>(), (int)step, (float)beta1, (float)beta2, (float)eps,
+                          (float)grad_scale, group_wd.data_ptr<float>(), decoupled ? 1 : 0, clip ? partials->data_ptr<double>() : nullptr,
+                          clip ? (float)max_norm : 0.f, static_cast<float*>(mptr(norm_out))),
+           "a4r_adamw_step");
 }
 
 // rank[u] = 1 + #{items i != target[u], i not in history(u), i >= 1 : score(u, i) > score(u, target[u])}  (metrics.py:82-116)
@@ -460,6 +495,9 @@ TORCH_LIBRARY(a4r, m) {
           "Tensor(a!) d_prec, Tensor(b!) d_emb, int B, int L, int E, bool cpc=False) -> ()", &score_bce_bwd);
     m.def("fused_adam_step(Tensor(a!) p, Tensor g, Tensor(b!) m, Tensor(c!) v, Tensor seg_end, Tensor seg_group, Tensor group_lr, int step, float beta1=0.9, "
           "float beta2=0.999, float eps=1e-8, float grad_scale=1.0) -> ()", &fused_adam_step);
+    m.def("fused_adamw_step(Tensor(a!) p, Tensor g, Tensor(b!) m, Tensor(c!) v, Tensor seg_end, Tensor seg_group, Tensor group_lr, Tensor group_wd, int step, "
+          "float beta1=0.9, float beta2=0.999, float eps=1e-8, float grad_scale=1.0, bool decoupled=True, Tensor(d!)? partials=None, float max_norm=0.0, "
+          "Tensor(e!)? norm_out=None) -> ()", &fused_adamw_step);
     m.def("topk_rank_eval(Tensor prec, Tensor item_emb, Tensor target, Tensor hist_ptr, Tensor hist_idx, Tensor(a!) rank) -> ()", &topk_rank_eval);
     m.def("topk_items(Tensor prec, Tensor item_emb, Tensor excl_ptr, Tensor excl_idx, int k) -> (Tensor, Tensor)", &topk_items);
     m.def("lora_bwd(Tensor x, Tensor dqa, Tensor dqb, Tensor Aa, Tensor Ab, Tensor BTa, Tensor BTb, float scale_a, float scale_b, Tensor(a!) dAa, Tensor(b!) dAb, "

@@ -17,6 +17,9 @@ def parse_args(argv=None):
     p.add_argument('--lr', type=float, default=1e-3)
     p.add_argument('--fine_tune_lr', type=float, default=1e-5)
     p.add_argument('--l2_weight', type=float, default=0)
+    p.add_argument('--optimizer', type=str, default='adam', choices=['adam', 'adamw'])      # FusedAdam (torch.optim.Adam) / FusedAdamW (AdamW)
+    p.add_argument('--weight_decay', type=float, default=0.0)          # per parameter of every group; coupled for adam, decoupled for adamw
+    p.add_argument('--max_grad_norm', type=float, default=0.0)         # > 0: clip the total gradient norm (clip_grad_norm_), logged with the loss
     p.add_argument('--drop_rate', type=float, default=0.1)
     p.add_argument('--CV_model_load', type=str, default='resnet-50')
     p.add_argument('--freeze_paras_before', type=int, default=45)

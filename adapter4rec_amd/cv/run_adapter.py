@@ -20,7 +20,7 @@ from ..data_utils.dataset import BuildTrainDataset
 from ..data_utils.utils import get_checkpoint, para_and_log, report_time_eval, report_time_train, save_model, setuplogger
 from ..ddp import FlatDDP, any_rank
 from ..inject import freeze_all
-from ..optim import FusedAdam
+from ..optim import from_args as optimizer_from_args
 from . import Model, ModelCPC, ViTForImageClassification, ViTMAEModel
 from .data_utils import eval_model, get_itemId_embeddings, get_itemLMDB_embeddings, open_image_db, read_behaviors, read_images
 from ..data_utils.metrics import write_recommendations
@@ -156,7 +156,7 @@ def train(args, use_modal, local_rank, Log_file, Log_screen, model_dir, start_ti
         train_dl = DataLoader(train_dataset, batch_size=args.batch_size, num_workers=0, sampler=sampler, collate_fn=_collate)
     model, start_epoch, ckpt2 = build_model(args, item_num, use_modal, cv_model, local_rank, Log_file, model_dir)
     model = FlatDDP(model, device_ids=[local_rank], output_device=local_rank)
-    optimizer = FusedAdam(optimizer_groups(model, args))
+    optimizer = optimizer_from_args(optimizer_groups(model, args), args)      # --optimizer / --weight_decay / --max_grad_norm; default: FusedAdam
     if ckpt2 is not None:
         optimizer.load_state_dict(ckpt2['optimizer'])
     steps_for_log, _ = para_and_log(model, len(users_train), args.batch_size, Log_file, args.logging_num, args.testing_num)
@@ -192,7 +192,8 @@ def train(args, use_modal, local_rank, Log_file, Log_screen, model_dir, start_ti
                     need_break = True
                     break
                 Log_file.info('cnt: {}, Ed: {}, batch loss: {:.5f}, sum loss: {:.5f}'.format(
-                    batch_index, batch_index * args.batch_size, loss.item() / batch_index, loss.item()))
+                    batch_index, batch_index * args.batch_size, loss.item() / batch_index, loss.item())
+                    + ('' if optimizer.last_grad_norm is None else ', grad norm: {:.5f}'.format(optimizer.last_grad_norm.item())))
             batch_index += 1
         if not need_break and any_rank(torch.isnan(loss)):                 # a NaN after the last log step: never evaluate / save NaN weights
             need_break = True

@@ -1,18 +1,58 @@
-"""FusedAdam: torch.optim.Adam's update (as configured at Downstream/Text/run.py:524-529: betas (0.9, 0.999),
-eps 1e-8, no weight decay, per-group lr) as ONE kernel launch over the engine's flat parameter / gradient
-buffers instead of ~4 small kernels per tensor.  Same constructor shape as torch.optim.Adam (param groups)."""
+"""FusedAdam / FusedAdamW: torch.optim.Adam's and AdamW's update as ONE kernel launch over the engine's flat parameter / gradient buffers instead of
+~4 small kernels per tensor.  Same constructor shape as torch.optim.Adam (param groups, per-group lr and weight_decay).  The reference's setting
+(Downstream/Text/run.py:524-529: betas (0.9, 0.999), eps 1e-8, no weight decay) runs a4r_adam_step exactly as it always has; weight decay or clipping
+switch to a4r_adamw_step (include/a4r.h)."""
+import math
+
 import torch
 
 from . import _lib as L
 
+# torch.optim.Adam arguments that have no fused form here: refused, never silently ignored
+_UNSUPPORTED = dict(amsgrad=False, maximize=False, capturable=False, differentiable=False, foreach=None, fused=None)
+
 
 class FusedAdam(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0):
-        if weight_decay != 0:
-            raise NotImplementedError('weight_decay: the reference uses none (run.py:524-529)')
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=0))
+    """torch.optim.Adam over the engine's flat buffers.
+
+    weight_decay: per param group; coupled (torch Adam: g += wd * p) or, with decoupled_weight_decay=True, decoupled (torch AdamW: p *= 1 - lr * wd).
+    max_grad_norm: clip the total gradient norm as torch.nn.utils.clip_grad_norm_(params, max_grad_norm) would before the step, without a host read:
+    a deterministic fp64 sum of squares (a4r_grad_sumsq), then the step scales every gradient by min(1, max_norm / (norm + 1e-6)) as it reads it.
+    Unlike clip_grad_norm_, p.grad (the flat gradient buffer) is NOT rewritten: after step() it still holds the unclipped gradients.
+    last_grad_norm is then a 0-d fp32 device tensor holding the pre-clip total norm (what clip_grad_norm_ returns), a new tensor each step; a
+    non-finite norm is not an error (error_if_nonfinite=False): the coefficient becomes NaN or 0 and the update proceeds -- check the norm.
+    The gradients are read as (g * grad_scale), so under FlatDDP every rank clips the same all-reduced buffer to the same bits."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, *, foreach=None, maximize=False,
+                 capturable=False, differentiable=False, fused=None, decoupled_weight_decay=False, max_grad_norm=None):
+        if max_grad_norm is not None and not (math.isfinite(max_grad_norm) and max_grad_norm > 0):
+            raise ValueError(f'max_grad_norm must be a finite positive number or None, got {max_grad_norm}')
+        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, foreach=foreach, maximize=maximize,
+                        capturable=capturable, differentiable=differentiable, fused=fused, decoupled_weight_decay=bool(decoupled_weight_decay))
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.last_grad_norm = None
+        super().__init__(params, defaults)
         self._bound = None
         self._step = 0
+
+    @staticmethod
+    def _check_group(g):
+        for k, off in _UNSUPPORTED.items():
+            if g.get(k, off) not in (off, False):
+                raise NotImplementedError(f'FusedAdam: {k}={g[k]!r} has no fused form (the update is one native kernel over the flat buffers)')
+        if not 0.0 <= float(g['weight_decay']):
+            raise ValueError(f'Invalid weight_decay value: {g["weight_decay"]}')
+
+    def add_param_group(self, param_group):
+        super().add_param_group(param_group)
+        self._check_group(self.param_groups[-1])
+
+    def __setstate__(self, state):                             # (load_state_dict: the groups take the checkpoint's hyper-parameters)
+        super().__setstate__(state)
+        for g in self.param_groups:
+            for k in ('weight_decay', 'decoupled_weight_decay', *_UNSUPPORTED):
+                g.setdefault(k, self.defaults[k])              # a checkpoint of an older FusedAdam holds lr / betas / eps / weight_decay only
+            self._check_group(g)
 
     # -- binding to the engine's flat buffers (parameters become views at the engine's first use)
     def _bind(self):
@@ -35,6 +75,9 @@ class FusedAdam(torch.optim.Optimizer):
         self._seg_group = torch.tensor([g for _, _, g in segs], dtype=torch.int32, device=dev)
         self._lr_host = None
         self._lr_dev = torch.zeros(len(self.param_groups), dtype=torch.float32, device=dev)
+        self._wd_host = None
+        self._wd_dev = torch.zeros(len(self.param_groups), dtype=torch.float32, device=dev)
+        self._partials = None
         self._m = torch.zeros_like(eng.flat_p)
         self._v = torch.zeros_like(eng.flat_p)
         covered = sum(m[2] for m in metas)
@@ -83,9 +126,28 @@ class FusedAdam(torch.optim.Optimizer):
             self._lr_dev.copy_(torch.tensor(lrs, dtype=torch.float32))
             self._lr_host = lrs
         g0 = self.param_groups[0]
+        wds = [float(g['weight_decay']) for g in self.param_groups]
         self._step += 1
-        L.adam_step(eng.flat_p, eng.flat_g, self._m, self._v, self._seg_end, self._seg_group, self._lr_dev, self._step,
-                    beta1=g0['betas'][0], beta2=g0['betas'][1], eps=g0['eps'], grad_scale=grad_scale)
+        if self.max_grad_norm is None and not any(wds):        # the reference's configuration: the plain Adam kernel, as it always ran
+            L.adam_step(eng.flat_p, eng.flat_g, self._m, self._v, self._seg_end, self._seg_group, self._lr_dev, self._step,
+                        beta1=g0['betas'][0], beta2=g0['betas'][1], eps=g0['eps'], grad_scale=grad_scale)
+            return
+        modes = {bool(g['decoupled_weight_decay']) for g in self.param_groups}
+        if len(modes) > 1:
+            raise NotImplementedError('FusedAdam: coupled and decoupled weight decay in one optimizer (one kernel updates every group)')
+        if wds != self._wd_host:
+            self._wd_dev.copy_(torch.tensor(wds, dtype=torch.float32))
+            self._wd_host = wds
+        norm = None
+        if self.max_grad_norm is not None:
+            if self._partials is None:
+                self._partials = torch.empty(L.GRAD_NORM_PARTS, dtype=torch.float64, device=eng.dev)
+            norm = torch.empty((), dtype=torch.float32, device=eng.dev)
+            L.grad_sumsq(eng.flat_g, self._partials, grad_scale=grad_scale)
+        L.adamw_step(eng.flat_p, eng.flat_g, self._m, self._v, self._seg_end, self._seg_group, self._lr_dev, self._wd_dev, self._step,
+                     beta1=g0['betas'][0], beta2=g0['betas'][1], eps=g0['eps'], grad_scale=grad_scale, decoupled=modes.pop(),
+                     partials=self._partials if norm is not None else None, max_norm=self.max_grad_norm or 0.0, norm_out=norm)
+        self.last_grad_norm = norm
 
     # -- checkpoint interchange with the reference (Downstream/Text/run.py:481-492, data_utils/utils.py:109-115): torch.optim.Adam's own
     #    layout -- state[param] = {step, exp_avg, exp_avg_sq} -- written and read; the per-parameter tensors are views of the flat moments
@@ -145,3 +207,28 @@ class FusedAdam(torch.optim.Optimizer):
             self._state_views()
         if pend.get('extra') and pend.get('late'):             # engine existed when the state was loaded; a lazily built
             self._bound.step_count = int(pend['extra'].get('engine_step_count', self._bound.step_count))   # one read p._a4r_resume_step
+
+
+class FusedAdamW(FusedAdam):
+    """torch.optim.AdamW over the engine's flat buffers: FusedAdam with decoupled weight decay and AdamW's default weight_decay=0.01."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, *, maximize=False, foreach=None,
+                 capturable=False, differentiable=False, fused=None, max_grad_norm=None):
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, foreach=foreach, maximize=maximize,
+                         capturable=capturable, differentiable=differentiable, fused=fused, decoupled_weight_decay=True, max_grad_norm=max_grad_norm)
+
+
+def from_args(param_groups, args):
+    """The optimizer of the entry points' --optimizer / --weight_decay / --max_grad_norm flags; the defaults (adam, 0, 0 = off) give FusedAdam(groups),
+    the reference's torch.optim.Adam."""
+    name = getattr(args, 'optimizer', 'adam')
+    wd = float(getattr(args, 'weight_decay', 0.0))
+    clip = float(getattr(args, 'max_grad_norm', 0.0))
+    kw = dict(max_grad_norm=clip) if clip > 0 else {}
+    if name == 'adamw':
+        return FusedAdamW(param_groups, weight_decay=wd, **kw)
+    if name != 'adam':
+        raise ValueError(f'--optimizer {name!r}: adam or adamw')
+    if wd:
+        kw['weight_decay'] = wd
+    return FusedAdam(param_groups, **kw)

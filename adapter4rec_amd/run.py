@@ -25,7 +25,7 @@ from .data_utils.utils import (get_checkpoint, para_and_log, report_time_eval, r
 from .ddp import FlatDDP, any_rank
 from .inject import freeze_all, inject_adapters, optimizer_groups
 from .model import BertBackbone, Model, ModelCPC
-from .optim import FusedAdam
+from .optim import from_args as optimizer_from_args
 from .parameters import parse_args
 
 DIMS = {'tiny': 128, 'mini': 256, 'medium': 512, 'base': 768, 'large': 1024}
@@ -130,7 +130,7 @@ def train(args, use_modal, local_rank, Log_file, Log_screen, model_dir, start_ti
                 items, mask = dev_sampler.sample(ids[i:i + args.batch_size])
                 yield items.view(-1, args.max_seq_len + 1, 2, items.size(-1)), mask
     model = FlatDDP(model, device_ids=[local_rank], output_device=local_rank)
-    optimizer = FusedAdam(optimizer_groups(model, args))
+    optimizer = optimizer_from_args(optimizer_groups(model, args), args)      # --optimizer / --weight_decay / --max_grad_norm; default: FusedAdam
     if ckpt2 is not None:
         optimizer.load_state_dict(ckpt2['optimizer'])
     Log_file.info(model)
@@ -162,7 +162,8 @@ def train(args, use_modal, local_rank, Log_file, Log_screen, model_dir, start_ti
                     need_break = True
                     break
                 Log_file.info('cnt: {}, Ed: {}, batch loss: {:.5f}, sum loss: {:.5f}'.format(
-                    batch_index, batch_index * args.batch_size, loss.item() / batch_index, loss.item()))
+                    batch_index, batch_index * args.batch_size, loss.item() / batch_index, loss.item())
+                    + ('' if optimizer.last_grad_norm is None else ', grad norm: {:.5f}'.format(optimizer.last_grad_norm.item())))
             batch_index += 1
         if not need_break and any_rank(torch.isnan(loss)):                 # a NaN after the last log step of the epoch: the reference checks
             need_break = True                                          # every batch (run.py:601-603); never evaluate / save NaN weights

@@ -393,10 +393,31 @@ int a4r_take_inputs(void* stream, const float* emb, float* out, int ldo, int B, 
 
 /* torch.optim.Adam as configured at Downstream/Text/run.py:524-529 (betas .9/.999, eps 1e-8, no decay)
  * over one flat fp32 buffer; element i belongs to the first segment with seg_end[seg] > i and uses
- * group_lr[seg_group[seg]].  g is multiplied by grad_scale first (1/world for the DDP average). */
+ * group_lr[seg_group[seg]].  g is multiplied by grad_scale first (1/world for the DDP average).  The same kernels as a4r_adamw_step, instantiated
+ * without decay and without clipping: the update is the one of earlier versions, bit for bit. */
 int a4r_adam_step(void* stream, float* p, const float* g, float* m, float* v, int64_t n,
                   const int32_t* seg_end, const int32_t* seg_group, int n_seg,
                   const float* group_lr, int step, float beta1, float beta2, float eps, float grad_scale);
+
+/* Gradient-norm clipping without a host read (new symbols; ABI 411 argument lists unchanged).
+ * a4r_grad_sumsq: partials[b], b < A4R_GRAD_NORM_PARTS (fp64, caller-allocated) = the sum of x * x over a fixed share of the elements, where
+ *   x = (float)(g[i] * grad_scale) and the square and the sums are taken in fp64 (the square of an fp32 value is exact there).  The shares and the
+ *   order of every sum are a function of n alone: the same n and data give the same partials bit for bit, on the 16-byte-load path (g 16-byte
+ *   aligned) and on the element path alike.  No float atomics.  n <= 0 or a NULL pointer: A4R_EINVAL.
+ * a4r_adamw_step: a4r_adam_step's update with weight decay group_wd[seg_group[seg]] (read like group_lr; non-NULL) and optional clipping:
+ *   decoupled 0: torch Adam(weight_decay): g += wd * p after clipping;  1: torch AdamW: p *= 1 - lr * wd before the moment update.
+ *   partials (a4r_grad_sumsq's output for this g and grad_scale, enqueued before on the same stream) or NULL = no clipping.  Each block reduces
+ *   the partials in the same fixed order: norm = sqrt(sum) in fp64 rounded once to fp32, coef = min(1, max_norm / (norm + 1e-6)) in fp32
+ *   (torch.nn.utils.clip_grad_norm_; NaN when the norm is NaN, 0 when it is infinite -- the update proceeds), and every gradient is multiplied by
+ *   coef after grad_scale.  g itself is not written.  norm_out (fp32 device scalar, may be NULL) receives the pre-clip norm.
+ *   A4R_EINVAL before any launch: a NULL pointer, n <= 0, n_seg <= 0, step < 1, decoupled not 0 / 1, partials given with max_norm not a finite
+ *   positive number, norm_out given without partials.  With every wd 0 and partials NULL the result equals a4r_adam_step's bit for bit. */
+#define A4R_GRAD_NORM_PARTS 1024
+int a4r_grad_sumsq(void* stream, const float* g, int64_t n, float grad_scale, double* partials);
+int a4r_adamw_step(void* stream, float* p, const float* g, float* m, float* v, int64_t n,
+                   const int32_t* seg_end, const int32_t* seg_group, int n_seg,
+                   const float* group_lr, int step, float beta1, float beta2, float eps, float grad_scale,
+                   const float* group_wd, int decoupled, const double* partials, float max_norm, float* norm_out);
 
 /* Refresh the kernel-side copies of trainable matrices after an optimiser step:
  * dst[rows_pad, cols_pad] (dtype) = src (fp32 [rows, cols] at flat + src_off) or its transpose, zero padded.
