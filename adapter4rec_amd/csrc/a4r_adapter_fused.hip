@@ -796,7 +796,6 @@ int launch_bwd(hipStream_t s, const AdBwdArgs& a, int grid) {
 
 }  // namespace
 
-int a4r_cu_count();       // a4r_gemm256.hip
 
 extern "C" int a4r_adapter_ln_fwd(void* stream, const void* A, int lda, const void* R1, int ldr1, const void* R2, int ldr2,
                                   const void* Wd, const float* bd, const void* Wu, const float* bu,

@@ -637,13 +637,11 @@ template <typename T, int DH, int WAVES>
 int launch_bwd(const Launch& L) {
     using C = AttnCfg<T, DH>;
     const a4r_attn_t& a = *L.a;
-    static const int pad = getenv("A4R_ATTN_BWD_LDS_PAD") ? atoi(getenv("A4R_ATTN_BWD_LDS_PAD")) : 0;      // occupancy experiment (tools/)
-    const int LDS = WAVES * (3 * 32 * C::GSTRIDE + 3 * 32 * C::PSTRIDE) + pad;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_kernel<T, DH, WAVES>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        attr_set = true;
+    constexpr int LDS = WAVES * (3 * 32 * C::GSTRIDE + 3 * 32 * C::PSTRIDE);
+    static bool lds_ok = false;                             // (set only once the opt-in has succeeded)
+    if (!lds_ok) {
+        if (int rc = a4r_set_lds(attn_bwd_kernel<T, DH, WAVES>, LDS)) return rc;
+        lds_ok = true;
     }
     const int total = a.n_items * a.n_heads;
     hipLaunchKernelGGL((attn_bwd_kernel<T, DH, WAVES>), dim3((total + WAVES - 1) / WAVES), dim3(WAVES * 64), LDS, L.s,
@@ -656,10 +654,10 @@ template <int DH, int WAVES>
 int launch_bwd_tr(const Launch& L) {
     const a4r_attn_t& a = *L.a;
     constexpr int LDS = WAVES * BtGeo<DH>::WAVE_LDS;
-    static bool attr_set = false;
-    if (!attr_set && LDS > 48 * 1024) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_tr_kernel<DH, WAVES>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        attr_set = true;
+    static bool lds_ok = false;
+    if (!lds_ok) {
+        if (int rc = a4r_set_lds(attn_bwd_tr_kernel<DH, WAVES>, LDS)) return rc;
+        lds_ok = true;
     }
     const int total = a.n_items * a.n_heads;
     hipLaunchKernelGGL((attn_bwd_tr_kernel<DH, WAVES>), dim3((total + WAVES - 1) / WAVES), dim3(WAVES * 64), LDS, L.s,
@@ -667,7 +665,6 @@ int launch_bwd_tr(const Launch& L) {
                        a.n_items, a.S, a.n_heads, a.causal, a.scale, a.mask_neg, a.drop_seed, a.drop_site, L.thr, L.ks, a.offsets);
     return a4r_launch_status();
 }
-const bool g_attn_bwd_tr = !(getenv("A4R_ATTN_BWD_TR") && atoi(getenv("A4R_ATTN_BWD_TR")) == 0);      // 0: the generic kernel for bf16 too (A/B, tests)
 
 int check(const a4r_attn_t* a, bool bwd) {
     if (!a || !a->qkv) return A4R_EINVAL;
@@ -706,12 +703,11 @@ extern "C" int a4r_attn_bwd(void* stream, const a4r_attn_t* a) {
     if (int e = check(a, true)) return e;
     if (a->dh <= 16) return a4r_attn_small(reinterpret_cast<hipStream_t>(stream), a, true);
     Launch L{reinterpret_cast<hipStream_t>(stream), a, a4r_thr16(a->drop_p), a4r_keep_scale(a->drop_p)};
-    if (a->dtype == A4R_BF16 && g_attn_bwd_tr) {
+    if (a->dtype == A4R_BF16) {
         // 4 waves per workgroup: 1 .. 4 measured the same (100 - 106 us at the text tower's shape), 6 and 12 (= all heads of an item in
         // one workgroup) 127 / 134 us -- a workgroup's LDS is only released when its slowest wave is done
         return a->dh == 64 ? launch_bwd_tr<64, 4>(L) : launch_bwd_tr<32, 4>(L);
     }
-    if (a->dtype == A4R_BF16) return a->dh == 64 ? launch_bwd<bf16_t, 64, 4>(L) : launch_bwd<bf16_t, 32, 4>(L);
     if (a->dh == 128) return launch_bwd<float, 128, 1>(L);
     if (a->dh == 256) return launch_bwd<float, 256, 1>(L);
     return a->dh == 64 ? launch_bwd<float, 64, 2>(L) : launch_bwd<float, 32, 4>(L);

@@ -521,14 +521,6 @@ template <int NKT> bool s_fits(int S) { return S <= NKT * 16 && S > 16 * kt_part
 template <typename T, int DH, int NKT> size_t lds_fwd() { return lds_main_fwd<T, DH, NKT>() + WG<NKT>::NWAVE * STG<T, DH>::BYTES; }
 template <typename T, int DH, int NKT> size_t lds_dq() { return lds_main_dq<T, DH, NKT>() + WG<NKT>::NWAVE * STG<T, DH>::BYTES; }
 template <typename T, int DH, int NKT> size_t lds_dkdv() { return lds_main_dkdv<T, DH, NKT>() + WG<NKT>::NWAVE * STG<T, DH>::BYTES; }
-constexpr size_t LDS_MAX = 160 * 1024;
-
-template <typename K> int set_lds(K kernel, size_t bytes) {
-    if (bytes > LDS_MAX) return A4R_EINVAL;
-    if (bytes > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess)
-        return A4R_ELAUNCH;
-    return A4R_OK;
-}
 
 Drop drop_of(const a4r_attn_t* a) {
     return Drop{a->drop_seed, a->drop_site, a4r_thr16(a->drop_p), a4r_keep_scale(a->drop_p)};
@@ -536,7 +528,7 @@ Drop drop_of(const a4r_attn_t* a) {
 
 template <typename T, int DH, int NKT, bool KM> int run_fwd_km(hipStream_t s, const a4r_attn_t* a, float* lse) {
     const size_t lds = lds_fwd<T, DH, NKT>();
-    if (int rc = set_lds(attn_long_fwd_kernel<T, DH, NKT, KM>, lds)) return rc;
+    if (int rc = a4r_set_lds(attn_long_fwd_kernel<T, DH, NKT, KM>, lds)) return rc;
     hipLaunchKernelGGL((attn_long_fwd_kernel<T, DH, NKT, KM>), dim3(a->n_items * a->n_heads), dim3(WG<NKT>::NTHR), lds, s, (const T*)a->qkv, a->ld, a->q_off,
                        a->k_off, a->v_off, (T*)a->out, a->ldo, lse, a->S, a->n_heads, a->scale, drop_of(a), (const float*)a->key_mask, a->causal);
     return a4r_launch_status();
@@ -548,8 +540,8 @@ template <typename T, int DH, int NKT> int run_fwd(hipStream_t s, const a4r_attn
 }
 template <typename T, int DH, int NKT, bool KM> int run_bwd_km(hipStream_t s, const a4r_attn_t* a, const float* lse, float* delta) {
     const size_t l1 = lds_dq<T, DH, NKT>(), l2 = lds_dkdv<T, DH, NKT>();
-    if (int rc = set_lds(attn_long_dq_kernel<T, DH, NKT, KM>, l1)) return rc;
-    if (int rc = set_lds(attn_long_dkdv_kernel<T, DH, NKT, KM>, l2)) return rc;
+    if (int rc = a4r_set_lds(attn_long_dq_kernel<T, DH, NKT, KM>, l1)) return rc;
+    if (int rc = a4r_set_lds(attn_long_dkdv_kernel<T, DH, NKT, KM>, l2)) return rc;
     const dim3 grid(a->n_items * a->n_heads), block(WG<NKT>::NTHR);
     if constexpr (sizeof(T) == 2 && DH == 64 && NKT == 14 && !KM) {
         // ViT-B/16's 197 tokens (129 .. 224): the one-pass backward (round 6, a4r_attn_long1.hip).  A4R_ATTN_BWD_ONEPASS=0 keeps the two launches (A/B runs, tests).
@@ -562,7 +554,7 @@ template <typename T, int DH, int NKT, bool KM> int run_bwd_km(hipStream_t s, co
     const bool fused = knob < 0 ? NKT <= 4 : knob != 0;
     if (fused) {
         const size_t l = l1 > l2 ? l1 : l2;
-        if (int rc = set_lds(attn_long_bwd_kernel<T, DH, NKT, KM>, l)) return rc;
+        if (int rc = a4r_set_lds(attn_long_bwd_kernel<T, DH, NKT, KM>, l)) return rc;
         hipLaunchKernelGGL((attn_long_bwd_kernel<T, DH, NKT, KM>), grid, block, l, s, (const T*)a->qkv, a->ld, a->q_off, a->k_off, a->v_off,
                            (const T*)a->dout, a->ldo, (const T*)a->out, lse, delta, (T*)a->dqkv, a->S, a->n_heads, a->scale, drop_of(a), (const float*)a->key_mask, a->causal);
         return a4r_launch_status();

@@ -409,16 +409,13 @@ extern "C" int a4r_debug_op_stamps(unsigned long long* host_out) {
 int a4r_attn_long_bwd1_launch(hipStream_t s, const a4r_attn_t* a, const float* lse) {
     constexpr int NKT = 14;
     using OP = OnePass<NKT>;
-    static int n_cu = 0;
-    if (!n_cu) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return A4R_ELAUNCH;
-        n_cu = prop.multiProcessorCount;
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(attn_long_bwd1_kernel<NKT, false>), hipFuncAttributeMaxDynamicSharedMemorySize, OP::BYTES) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(attn_long_bwd1_kernel<NKT, true>), hipFuncAttributeMaxDynamicSharedMemorySize, OP::BYTES) != hipSuccess) return A4R_ELAUNCH;
+    static bool lds_ok = false;                             // (set only once both opt-ins have succeeded)
+    if (!lds_ok) {
+        if (int rc = a4r_set_lds(attn_long_bwd1_kernel<NKT, false>, OP::BYTES)) return rc;
+        if (int rc = a4r_set_lds(attn_long_bwd1_kernel<NKT, true>, OP::BYTES)) return rc;
+        lds_ok = true;
     }
-    const int n_pairs = a->n_items * a->n_heads;
+    const int n_pairs = a->n_items * a->n_heads, n_cu = a4r_cu_count_raw();
     const int grid = n_pairs < n_cu ? n_pairs : n_cu;
     const Drop dr{a->drop_seed, a->drop_site, a4r_thr16(a->drop_p), a4r_keep_scale(a->drop_p)};
     if (dr.thr16)

@@ -324,3 +324,30 @@ A4R_DEV float group16_max(float v) {
     for (int o = 8; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
     return v;
 }
+
+// ---------------------------------------------------------------- host-side launch helpers
+// CUs of the current device (256 if the query fails), cached per device id
+inline int a4r_cu_count_raw() {
+    static int cache[16] = {0};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) dev = 0;
+    int& n = cache[dev];
+    if (!n) {
+        hipDeviceProp_t prop;
+        n = hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    }
+    return n;
+}
+// the grid of a persistent launch: the CU count rounded down to a multiple of 8 (a workgroup stays on one XCD group), cached once per process
+inline int a4r_cu_count() {
+    static const int n = [] { const int r = a4r_cu_count_raw() & ~7; return r < 8 ? 8 : r; }();
+    return n;
+}
+// dynamic-LDS opt-in for a launch of `bytes`: A4R_EINVAL above the CU's 160 KiB, hipFuncSetAttribute above the default 48 KiB
+// (A4R_ELAUNCH if it fails); a caller that caches the result sets its flag only after A4R_OK
+template <typename K> int a4r_set_lds(K kernel, size_t bytes) {
+    if (bytes > 160 * 1024) return A4R_EINVAL;
+    if (bytes > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess)
+        return A4R_ELAUNCH;
+    return A4R_OK;
+}

@@ -275,7 +275,6 @@ int a4r_gemm_nt_256(hipStream_t s, const a4r_gemm_t& g);   // a4r_gemm256.hip
 int a4r_gemm_nt_skinny64(hipStream_t s, const a4r_gemm_t& g); // a4r_gemm_skinny.hip (N == 64, bf16 in: the adapter down-projections)
 int a4r_gemm_nt_skinnyk(hipStream_t s, const a4r_gemm_t& g);  // a4r_gemm_skinny.hip (K == 64, bf16: the adapter up-projections)
 static int run_256(hipStream_t s, const a4r_gemm_t& g);
-int a4r_cu_count();                                          // a4r_gemm256.hip: CU count rounded down to a multiple of 8
 extern "C" int a4r_gemm_tail_plan(int M, int N, int* p_full, int* kp);   // a4r_gemm256.hip: 1 = the launch cuts its last partial round into short tiles
 
 static int run_256(hipStream_t s, const a4r_gemm_t& g) { return a4r_gemm_nt_256(s, g); }

@@ -678,29 +678,15 @@ __global__ void __launch_bounds__(512, 2) gemm_nt_256_kernel(const a4r_gemm_t p,
 
 }  // namespace
 
-int a4r_cu_count() {
-    static int n_cu = 0;
-    if (n_cu == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n_cu = prop.multiProcessorCount;
-        if (n_cu <= 0) n_cu = 256;
-        n_cu &= ~7;                                        // multiple of 8: a workgroup stays on one XCD group
-        if (n_cu < 8) n_cu = 8;
-    }
-    return n_cu;
-}
-
 // Short-tile tail of a launch.  tiles = R full rounds of the persistent grid + a partial one: the first p_full = floor(R * grid / ntn) row
 // panels keep 256-row tiles (<= R per workgroup), the rows behind them are cut into tiles of 32 * kp rows with the smallest kp that needs at
 // most one tile per workgroup -- R + f(kp) tile periods instead of R + 1.  Measured (tools/gemm_tail_probe.py, one tile per CU, all CUs):
 // f = 0.61 - 0.70 at kp = 1, 0.81 at kp = 4, 0.96 - 0.98 at kp = 7 -- a K-tile's DMA issue, fragment reads and barriers do not shrink with
-// the MFMA count -- so the split is used for kp <= 3 only (A4R_GEMM_TAIL = the largest kp, default 3, 0 = never; at kp = 4 - 7 the BERT step
+// the MFMA count -- so the split is used for kp <= 3 only (a4r_gemm_tail_max = the largest kp, default 3, 0 = never; at kp = 4 - 7 the BERT step
 // lost 2 %: the gain is below what the banded tile map, which a tail excludes, is worth on the N = 3072 launches).  A function of (M, N)
 // and the CU count only: the launch that writes a tile-native 8-bit derivative and the one that reads it agree on the split.
-static int g_tail_max = -1;
+static int g_tail_max = 3;
 extern "C" int a4r_gemm_tail_max(int k) {
-    if (g_tail_max < 0) g_tail_max = getenv("A4R_GEMM_TAIL") ? atoi(getenv("A4R_GEMM_TAIL")) : 3;
     const int old = g_tail_max;
     if (k >= 0) g_tail_max = k < 7 ? k : 7;
     return old;
@@ -740,32 +726,23 @@ int a4r_gemm_w4(int v) {            // v = 0 / 1 sets, anything else queries (a4
 
 namespace {
 
-int g_band = -1;        // A4R_GEMM_BAND: -1 = automatic, 0 = panel-major map always, n > 0 = bands of n N-tiles wherever the banded map applies
-
 // Band width of the banded tile map, or 0 for the panel-major map.  Banding needs whole panels per XCD without costing a round:
 // the slowest XCD must not run more rounds than the balanced map would.
 static int band_for(const a4r_gemm_t& g, int ntm, int ntn, int grid, int isz) {
-    if (g_band < 0) {
-        const char* e = getenv("A4R_GEMM_BAND");
-        g_band = e ? atoi(e) + 1000 : 999;                 // 999 = automatic (resolved per shape below)
-    }
-    if (g_band == 1000 || grid % 8) return 0;
+    if (grid % 8) return 0;
     const int wg_x = grid / 8;
     const int max_len = (ntm / 8 + (ntm % 8 ? 1 : 0)) * ntn;
     const int rounds_bal = (ntm * ntn + grid - 1) / grid, rounds_band = (max_len + wg_x - 1) / wg_x;
     if (ntm < 8 || rounds_band > rounds_bal) return 0;
-    if (g_band > 1000) return g_band - 1000 < ntn ? g_band - 1000 : ntn;
-    // automatic, long outputs (>= 128 row panels = 16 per XCD: the text tower at 32 users, the image tower): whole row panels per XCD walked in
-    // bands of THREE N-tiles for every N (round 4, same-box sweeps of A4R_GEMM_BAND over all workloads, profiles/r04_m_band_sweep.txt: BERT-base
+    // long outputs (>= 128 row panels = 16 per XCD: the text tower at 32 users, the image tower): whole row panels per XCD walked in
+    // bands of THREE N-tiles for every N (round 4, same-box sweeps of the band width over all workloads, profiles/r04_m_band_sweep.txt: BERT-base
     // 17.21 -> 17.00 ms, RoBERTa 17.55 -> 17.27, BERT fp8 15.32 -> 15.17, ViT + LoRA +-0; at 66 row panels -- ViT-MAE -- the same policy costs
     // 1.4 %, so shorter outputs keep the rule below).  A 3-tile B band is 1.2 MB at K = 768: it stays in the XCD's L2 whatever the A stream does,
     // and the A panels it re-reads (4 x at N = 3072) come from the Infinity Cache.
-    static const int long_band = getenv("A4R_GEMM_BAND_LONG") ? atoi(getenv("A4R_GEMM_BAND_LONG")) : 3;
-    if (long_band > 0 && ntm >= 128) return long_band < ntn ? long_band : ntn;
-    // shorter outputs: band only when the whole B operand does not sit in an XCD's L2 next to the streaming A panels
-    // (A4R_GEMM_BAND_FIT / A4R_GEMM_BAND_BYTES: the two thresholds, bytes -- A/B sweeps)
-    static const double fit = getenv("A4R_GEMM_BAND_FIT") ? atof(getenv("A4R_GEMM_BAND_FIT")) : 4.0e6;
-    static const double budget = getenv("A4R_GEMM_BAND_BYTES") ? atof(getenv("A4R_GEMM_BAND_BYTES")) : 2.5e6;
+    if (ntm >= 128) return 3 < ntn ? 3 : ntn;
+    // shorter outputs: band only when the whole B operand (above `fit` bytes) does not sit in an XCD's L2 next to the streaming A panels;
+    // bands of `budget` bytes of B
+    const double fit = 4.0e6, budget = 2.5e6;
     const double b_tile = 256.0 * g.K * isz;
     if (b_tile * ntn <= fit) return 0;                      // (N = 2304, K = 768: 3.5 MB still shares an L2 with the A stream: PMC 250 MB read un-banded vs 339 banded)
     int gn = (int)(budget / b_tile);
@@ -787,18 +764,16 @@ int launch256(hipStream_t s, const a4r_gemm_t& g) {
         if (p_full == 0) grid = (n_tail + 7) & ~7;
         ntm = p_full;
     }
-    static const int no_stream = getenv("A4R_GEMM_NO_STREAM") ? atoi(getenv("A4R_GEMM_NO_STREAM")) != 0 : 0;
-    static const int stagger_pct = getenv("A4R_GEMM_STAGGER") ? atoi(getenv("A4R_GEMM_STAGGER")) : 50;     // (30 until the end of round 4; re-swept after the band policy: LOG.md part D)
+    const int stagger_pct = 50;                            // (30 until the end of round 4; re-swept after the band policy: LOG.md part D)
     int delay = 0;
-    if (stagger_pct > 0 && ntm * ntn > 2 * grid) {         // (tile period in 10-ns ticks ~ 145 per K-tile of 128 B + 400)
+    if (ntm * ntn > 2 * grid) {                            // (tile period in 10-ns ticks ~ 145 per K-tile of 128 B + 400)
         delay = (int)((g.K * (int)sizeof(TI) / 128 * 145 + 400) * stagger_pct / 100);
         if (delay > 16383) delay = 16383;
     }
     // (with a short-tile tail the panel-major map -- whole panels per XCD would leave the XCDs uneven numbers of full tiles --, EXCEPT when the full
-    // panels divide evenly over the 8 XCDs: the image tower's 259 panels = 256 full + a tail, 32 per XCD; round 4, A4R_GEMM_BAND_TAIL=0 = never)
-    static const int band_tail = getenv("A4R_GEMM_BAND_TAIL") ? atoi(getenv("A4R_GEMM_BAND_TAIL")) != 0 : 1;
-    const bool band_ok = tail_kp == 0 || (band_tail && sizeof(TI) == 2 && ntm > 0 && ntm % 8 == 0 && grid == n_cu);   // (ViT + LoRA same box: bf16 30.16 -> 30.05 ms; e4m3 +0.4 %: bf16 only)
-    const int gn = (band_ok ? band_for(g, ntm, ntn, grid, (int)sizeof(TI)) : 0) | (no_stream << 16) | (delay << 17);
+    // panels divide evenly over the 8 XCDs: the image tower's 259 panels = 256 full + a tail, 32 per XCD; round 4)
+    const bool band_ok = tail_kp == 0 || (sizeof(TI) == 2 && ntm > 0 && ntm % 8 == 0 && grid == n_cu);   // (ViT + LoRA same box: bf16 30.16 -> 30.05 ms; e4m3 +0.4 %: bf16 only)
+    const int gn = (band_ok ? band_for(g, ntm, ntn, grid, (int)sizeof(TI)) : 0) | (delay << 17);      // (bit 16, the kernel's no-stream flag: 0)
 #ifdef A4R_WITH_W4
     if constexpr (sizeof(TI) == 2) {                       // bf16 operands: the four-wave kernel (a4r_gemm256w4.hip) where it applies and is switched on
         const int nk = g.K / 64;
@@ -821,10 +796,9 @@ static int epi_mask(const a4r_gemm_t& g) {
 template <typename T>
 int dispatch_same(hipStream_t s, const a4r_gemm_t& g) {   // in == out dtype: the activation forms the training step uses
     // bf16 (the training step): the epilogue forms the step launches by the dozen get instantiations WITHOUT the run-time tests of the
-    // pieces they do not carry (A4R_GEMM_GENERIC_EPI=1: the all-purpose instantiation always)
-    static const int generic = getenv("A4R_GEMM_GENERIC_EPI") ? atoi(getenv("A4R_GEMM_GENERIC_EPI")) != 0 : 0;
+    // pieces they do not carry; any other combination takes the all-purpose instantiation below
     if constexpr (sizeof(T) == 2) {
-        const int m = generic ? -1 : epi_mask(g);
+        const int m = epi_mask(g);
         if (g.act == A4R_ACT_NONE && g.dact == A4R_ACT_NONE) {
             if (m == 0) return launch256<T, T, A4R_ACT_NONE, A4R_ACT_NONE, 0>(s, g);
             if (m == 1) return launch256<T, T, A4R_ACT_NONE, A4R_ACT_NONE, 1>(s, g);

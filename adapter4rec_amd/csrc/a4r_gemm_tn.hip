@@ -269,11 +269,8 @@ __global__ void __launch_bounds__(256) colsum_kernel(const T* __restrict__ X, in
 
 int g_tn_variant = 1;          // 0: register-staged kernel for bf16 too (tests / A-B via a4r_gemm_variant(0))
 
-// 1 when the launch's (token range, product) groups can be dealt whole to the 8 XCDs (A4R_TN_XCD=0: launch order, A/B runs)
-static int tn_xcd_groups(int groups) {
-    static const int on = getenv("A4R_TN_XCD") ? atoi(getenv("A4R_TN_XCD")) != 0 : 1;
-    return on && groups % 8 == 0;
-}
+// 1 when the launch's (token range, product) groups can be dealt whole to the 8 XCDs
+static int tn_xcd_groups(int groups) { return groups % 8 == 0; }
 
 // a4r_gemm_tn256.hip: the 256 x 256-tile kernel for large outputs (weight gradients of trainable backbone Linears)
 int a4r_tn256_takes(int M, int P, int Q, int dtype);
@@ -318,8 +315,7 @@ extern "C" int a4r_gemm_tn2(void* stream, const void* X1, int ldx1, const void* 
         return A4R_EINVAL;
     if ((reinterpret_cast<uintptr_t>(X1) | reinterpret_cast<uintptr_t>(Y1) | reinterpret_cast<uintptr_t>(X2) | reinterpret_cast<uintptr_t>(Y2)) & 15u) return A4R_EINVAL;
     const int tiles = (P1 / 64) * (Q1 / 64);
-    static const int wgs_env = getenv("A4R_TN2_WGS") ? atoi(getenv("A4R_TN2_WGS")) : 384;                 // (A/B runs)
-    const int wgs_per_product = wgs_env > 0 ? wgs_env : 384;                                                // (0 / not a number / negative: the default)
+    const int wgs_per_product = 384;
     int splits = (wgs_per_product + tiles - 1) / tiles;     // two products: half the splits of the single-product launch each
     const int stages = M / 64;
     if (splits > stages) splits = stages;

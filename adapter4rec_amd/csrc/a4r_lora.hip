@@ -322,8 +322,6 @@ __global__ void __launch_bounds__(256) lora_reduce_kernel(const LoraBwdArgs p, i
 
 }  // namespace
 
-int a4r_cu_count();       // a4r_gemm256.hip
-
 extern "C" int a4r_lora_bwd_fused_ws_floats(int H) { return a4r_cu_count() * WS_ROWS2 * H; }
 
 extern "C" int a4r_lora_bwd_fused(void* stream, const void* x, int ldx, const void* dqa, const void* dqb, int lddq,
@@ -345,11 +343,11 @@ extern "C" int a4r_lora_bwd_fused(void* stream, const void* x, int ldx, const vo
                         (const bf16_t*)BTb, ldw, scale_a, scale_b, dAa, dAb, lda, dBa, dBb, ldb, dbias_a, dbias_b, ldbias, M, ws};
     constexpr size_t lds1 = 2 * sizeof(float) * 8 * 2 * 16 * 16 + 8 * 3 * 16 * SLAB_LD + 8 * 2 * 16 * 20 * sizeof(unsigned short);
     constexpr size_t lds2 = sizeof(float) * 8 * 4 * 16 * 16 + 8 * 3 * 16 * SLAB_LD + 8 * 4 * 16 * 20 * sizeof(unsigned short);
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(lora_bwd_kernel<96, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1) != hipSuccess) return A4R_ELAUNCH;
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(lora_bwd2_kernel<96, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2) != hipSuccess) return A4R_ELAUNCH;
-        attr_set = true;
+    static bool lds_ok = false;                             // (set only once both opt-ins have succeeded)
+    if (!lds_ok) {
+        if (int rc = a4r_set_lds(lora_bwd_kernel<96, 8>, lds1)) return rc;
+        if (int rc = a4r_set_lds(lora_bwd2_kernel<96, 8>, lds2)) return rc;
+        lds_ok = true;
     }
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (wide) hipLaunchKernelGGL((lora_bwd2_kernel<96, 8>), dim3(grid), dim3(512), lds2, s, p);

@@ -701,9 +701,8 @@ template <auto Kernel> int resident_grid(int rows) {         // (the kernel is a
     int& cap = caps[dev];
     if (!cap) {
         int per_cu = 0;
-        hipDeviceProp_t pr;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, Kernel, 256, 0) != hipSuccess || per_cu < 1) per_cu = 4;
-        cap = (hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0 ? pr.multiProcessorCount : 256) * per_cu;
+        cap = a4r_cu_count_raw() * per_cu;
     }
     const int g = (rows + 3) / 4;
     return g > cap ? cap : (g < 1 ? 1 : g);
@@ -852,14 +851,8 @@ extern "C" int a4r_ln_bwd(void* stream, const void* dy, int lddy, const void* v,
                                (const float*)dres, lddres, (float*)dv, lddv, M, H);
         return a4r_launch_status();
     }
-    static const int pg_on = getenv("A4R_LN_PG") ? atoi(getenv("A4R_LN_PG")) != 0 : 1;          // (A/B runs: 0 = ln_bwd_kernel)
-    if (pg_on && wgb && !wdb && !add && !thr && M >= 2048) {     // trainable LayerNorm of an un-adapted sub-layer: parameter gradients on lean loads
-        int dev = 0, ncu = 256;
-        hipDeviceProp_t pr;
-        static int ncu_c[16] = {0};                          // per device id
-        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) dev = 0;
-        if (!ncu_c[dev]) ncu_c[dev] = (hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0) ? pr.multiProcessorCount : 256;
-        ncu = ncu_c[dev];
+    if (wgb && !wdb && !add && !thr && M >= 2048) {          // trainable LayerNorm of an un-adapted sub-layer: parameter gradients on lean loads
+        const int ncu = a4r_cu_count_raw();
         int g8 = (M + 7) / 8; if (g8 > ncu) g8 = ncu;
         const uint32_t thr2 = a4r_thr16(drop2_p);
         const float sc2 = a4r_keep_scale(drop2_p);

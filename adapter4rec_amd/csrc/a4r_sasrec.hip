@@ -676,10 +676,6 @@ int fill(const a4r_sasrec_block_t* b, int T, int train, BlockW& w, int& dpe) {
     w.site = b->drop_site; w.seed = b->drop_seed;
     return A4R_OK;
 }
-
-template <typename K> int set_lds(K kernel, size_t bytes) {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess ? A4R_OK : A4R_ELAUNCH;
-}
 }  // namespace
 
 extern "C" int a4r_sasrec_block_fwd(void* stream, const a4r_sasrec_block_t* b, const float* x, const float* log_mask, float* y,
@@ -693,10 +689,10 @@ extern "C" int a4r_sasrec_block_fwd(void* stream, const a4r_sasrec_block_t* b, c
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const bool tr = w.thr_attn || w.thr_hidden;
     if (tr) {
-        if (int rc = set_lds(sasrec_block_fwd_kernel<true>, lds)) return rc;
+        if (int rc = a4r_set_lds(sasrec_block_fwd_kernel<true>, lds)) return rc;
         hipLaunchKernelGGL(sasrec_block_fwd_kernel<true>, dim3(n_users), dim3(256), lds, s, x, log_mask, y, w, T, dpe);
     } else {
-        if (int rc = set_lds(sasrec_block_fwd_kernel<false>, lds)) return rc;
+        if (int rc = a4r_set_lds(sasrec_block_fwd_kernel<false>, lds)) return rc;
         hipLaunchKernelGGL(sasrec_block_fwd_kernel<false>, dim3(n_users), dim3(256), lds, s, x, log_mask, y, w, T, dpe);
     }
     return a4r_launch_status();
@@ -719,10 +715,10 @@ extern "C" int a4r_sasrec_block_bwd(void* stream, const a4r_sasrec_block_t* b, c
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const bool tr = w.thr_attn || w.thr_hidden;
     if (tr) {
-        if (int rc = set_lds(sasrec_block_bwd_kernel<true>, lds)) return rc;
+        if (int rc = a4r_set_lds(sasrec_block_bwd_kernel<true>, lds)) return rc;
         hipLaunchKernelGGL(sasrec_block_bwd_kernel<true>, dim3(n_users), dim3(256), lds, s, x, log_mask, dy, dx, w, g, T, dpe);
     } else {
-        if (int rc = set_lds(sasrec_block_bwd_kernel<false>, lds)) return rc;
+        if (int rc = a4r_set_lds(sasrec_block_bwd_kernel<false>, lds)) return rc;
         hipLaunchKernelGGL(sasrec_block_bwd_kernel<false>, dim3(n_users), dim3(256), lds, s, x, log_mask, dy, dx, w, g, T, dpe);
     }
     return a4r_launch_status();

@@ -219,15 +219,9 @@ int topk_cap(int K) {                                // candidate slots per user
     return c;
 }
 
-template <typename Kern> int set_lds(Kern kernel, size_t bytes) {
-    if (bytes > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess)
-        return A4R_ELAUNCH;
-    return A4R_OK;
-}
-
 template <int E> int launch_partial(hipStream_t s, dim3 grid, size_t lds, const float* prec, const float* item_emb, const int32_t* excl_ptr,
                                     const int32_t* excl_idx, uint64_t* ws, int U, int N1, int K, int cap) {
-    if (int rc = set_lds(topk_partial_kernel<E>, lds)) return rc;
+    if (int rc = a4r_set_lds(topk_partial_kernel<E>, lds)) return rc;
     hipLaunchKernelGGL(topk_partial_kernel<E>, grid, dim3(256), lds, s, prec, item_emb, excl_ptr, excl_idx, ws, U, N1, K, cap);
     return A4R_OK;
 }
@@ -264,7 +258,7 @@ extern "C" int a4r_topk_items(void* stream, const float* prec, const float* item
         hipLaunchKernelGGL(topk_decode_kernel, dim3(blocks), dim3(256), 0, s, w, ids, scores, n);
     } else {
         const size_t mlds = (size_t)gy * K * sizeof(uint64_t);
-        if ((rc = set_lds(topk_merge_kernel, mlds))) return rc;
+        if ((rc = a4r_set_lds(topk_merge_kernel, mlds))) return rc;
         hipLaunchKernelGGL(topk_merge_kernel, dim3(U), dim3(256), mlds, s, w, ids, scores, U, K, gy);
     }
     return a4r_launch_status();

@@ -16,6 +16,7 @@ Data layout in HBM
     of the adapter matrices are refreshed by one pack launch per step.
 """
 import math
+import os as _os
 
 import torch
 
@@ -30,10 +31,12 @@ def pad_to(n, m):
     return (n + m - 1) // m * m
 
 
-import os as _os
-TN2 = bool(int(_os.environ.get('A4R_TN2', '1')))                       # an adapter's two weight gradients in one launch (0: two a4r_gemm_tn, A/B)
-TN2_BIAS = bool(int(_os.environ.get('A4R_TN2_BIAS', '1')))             # an adapter's two bias gradients from its weight-gradient launch (0: from the fused backward's end-of-launch flush, A/B)
-FUSE_BD = bool(int(_os.environ.get('A4R_FUSE_BD', '1')))               # db_down from the fused adapter backward kernel (0: a4r_colsum launches, A/B)
+def _skip_unused_items():
+    """A4R_SKIP_UNUSED_ITEMS, read at call time: '0' encodes every item slot, '2' forces the compact batch, anything else decides by shape
+    (TransRecEngine._kept_rows)."""
+    return _os.environ.get('A4R_SKIP_UNUSED_ITEMS', '1')
+
+
 WGRAD_STREAM = bool(int(_os.environ.get('A4R_WGRAD_STREAM', '0')))     # 1 = adapter weight gradients on a side stream (see _adapter_wgrads): +1.3 % in round 1, neutral since the GEMM's
                                                                         # late-starting workgroups use the same idle CUs (same-box 19.07 vs 18.98 ms): off by default
 
@@ -82,7 +85,7 @@ class _Adapter:
         # instruction of those kernels' prologues then reads 1 KiB contiguous; the first tile of a launch starts ~3 us earlier).  Row-major copies stay:
         # the three-launch forms, the weight-gradient kernels' shapes and the tests read them.  (fwd: wd, wu; bwd: wuT, wdT)
         self.frag_f = self.frag_b = None
-        if dt == torch.bfloat16 and self.dp == 64 and width in (128, 256, 512, 768, 1024) and _os.environ.get('A4R_ADAPTER_FRAG', '1') != '0':
+        if dt == torch.bfloat16 and self.dp == 64 and width in (128, 256, 512, 768, 1024):
             mk = lambda: torch.zeros(64 * width, dtype=dt, device=dev)
             self.frag_f, self.frag_b = (mk(), mk()), (mk(), mk())
         if self.virtual is None:
@@ -123,7 +126,6 @@ class _Lora:
     every step (so forward and dgrad cost nothing extra); the low-rank gradients come from four skinny products in backward:
     t = x A^T, dt = (dq B) s, dB = dq^T t s, dA = dt^T x."""
 
-    SHARE = _os.environ.get('A4R_LORA_SHARE', '1') != '0'
     ONES_COL = 32            # (shared form: rank columns 0 - 7 and 16 - 23 are in use)
 
     def __init__(self, mod, width, eng, dt, slot, share=None):
@@ -173,7 +175,7 @@ class _Lora:
         """The _Lora objects of a block's (query, key, value) projections; two small-rank ones share their A-side launches."""
         idx = [i for i, lin in enumerate(lins) if type(lin).__name__ == 'LoRALinear']
         small = [i for i in idx if 0 < lins[i].r <= 16]
-        share = {} if (cls.SHARE and len(small) == 2 and len(idx) == 2) else None
+        share = {} if (len(small) == 2 and len(idx) == 2) else None
         out = []
         for i in idx:
             out.append(cls(lins[i], width, eng, dt, i, share=(share, 16 * small.index(i)) if share is not None else None))
@@ -248,7 +250,7 @@ class TransRecEngine:
         # GEMMs whose input is a LayerNorm output (qkv, FFN-up); everything else, and all of backward, is the bf16 path
         self.fp8 = dtype == 'fp8'
         # bf16 storage: the saved GELU derivative of the encoder FFNs is kept as 8-bit fixed point (include/a4r.h c2_mode 2)
-        self.q8_deriv = dtype != 'fp32' and _os.environ.get('A4R_Q8_DERIV', '1') != '0'
+        self.q8_deriv = dtype != 'fp32'
         self.T = torch.float32 if dtype == 'fp32' else torch.bfloat16
         # --residual_dtype fp32 (bf16 storage): fp32 twins of the residual stream, keyed by the bf16 tensor they shadow (see _sub_forward)
         self.res32 = dtype != 'fp32' and getattr(args, 'residual_dtype', 'bf20') == 'fp32'
@@ -277,8 +279,6 @@ class TransRecEngine:
         self.step_count = 0
         self._packs_T, self._packs_b, self._virtual = [], [], []
         self._arena, self._arena_used, self._corners, self._corner_tab = [], 0, [], None
-        # one-launch adapter + residual + LayerNorm kernels (a4r_adapter_fused.hip); A4R_FUSE_ADAPTERS=0: the three-launch forms (A/B runs, tests)
-        self.fuse_adapters = bool(int(_os.environ.get('A4R_FUSE_ADAPTERS', '1'))) and bool(getattr(args, 'fuse_adapters', True))
         self._collect_trainables()
         for p in self.trainable_params:            # resumed run (FusedAdam.load_state_dict): the counter-based dropout stream continues
             if getattr(p, '_a4r_resume_step', None) is not None:
@@ -328,14 +328,13 @@ class TransRecEngine:
         # (pre-LN image tower: engine_vit.py -- both fp8 GEMM inputs are LayerNorm outputs; post-LN text tower: _block_forward below -- the
         # block input and the attention-output sub-layer's LayerNorm output leave the fused adapter kernel as e4m3 + row scale)
         ok = lambda w: w.shape[0] % 256 == 0 and w.shape[1] % 128 == 0
-        more = _os.environ.get('A4R_FP8_MORE', '1') != '0'              # 0: round 2's coverage (forward qkv + FFN-up only; A/B runs)
         for b in self.bert_blocks:
             b.wqkv8 = b.wi8 = b.wo8 = b.wo28 = b.wo2T8 = b.wiT8 = None
             b.wqkv8_dyn = False
             frozen_qkv = not b.lora and all(d is not None and not d.trainable for d in b.qkv)
             if frozen_qkv and ok(b.wqkv):
                 b.wqkv8, b.wqkv8s = L.quantize_weight_fp8(b.wqkv)
-            elif more and b.lora and all(d is None or not d.trainable for d in b.qkv) and ok(b.wqkv):       # (None: a LoRA-carrying slot)
+            elif b.lora and all(d is None or not d.trainable for d in b.qkv) and ok(b.wqkv):       # (None: a LoRA-carrying slot)
                 # LoRA on q / v (configs[2]): the FORWARD operand is the merged W + B A / r, re-quantised after every merge (pack_trainables:
                 # one row pass over [3H, H] per layer); the LoRA gradients and dx keep using the bf16 operands
                 b.wqkv8 = torch.zeros(b.wqkv.shape, dtype=torch.uint8, device=b.wqkv.device)
@@ -343,9 +342,9 @@ class TransRecEngine:
                 b.wqkv8_dyn = True
             if not b.d_i.trainable and ok(b.wi):
                 b.wi8, b.wi8s = L.quantize_weight_fp8(b.wi)
-            if more and not b.d_o.trainable and ok(b.wo):
+            if not b.d_o.trainable and ok(b.wo):
                 b.wo8, b.wo8s = L.quantize_weight_fp8(b.wo)
-            if more and b.wi8 is not None and not b.d_o2.trainable and ok(b.wo2) and ok(b.wo2T) and ok(b.wiT) and self._q8(b):
+            if b.wi8 is not None and not b.d_o2.trainable and ok(b.wo2) and ok(b.wo2T) and ok(b.wiT) and self._q8(b):
                 b.wo28, b.wo28s = L.quantize_weight_fp8(b.wo2)          # forward FFN-down  [H, F]
                 b.wo2T8, b.wo2T8s = L.quantize_weight_fp8(b.wo2T)       # d FFN-down        [F, H]: rows = columns of du
                 b.wiT8, b.wiT8s = L.quantize_weight_fp8(b.wiT)          # d FFN-up          [H, F]
@@ -577,9 +576,6 @@ class TransRecEngine:
     def _w(self, t, dt=None):
         return t.detach().to(self.dev, dt or self.T).contiguous()
 
-    def _wT(self, t, dt=None):
-        return t.detach().to(self.dev, dt or self.T).t().contiguous()
-
     def _f32(self, t):
         return t.detach().to(self.dev, torch.float32).contiguous()
 
@@ -748,13 +744,11 @@ class TransRecEngine:
             self.sas_kads = [self._make_kadapter(m, E, self.Lseq - 1, f32, 5000 + 64 * j) for j, m in enumerate(tbs.adapter_list)]
             self.d_com2 = _Dense(self, tbs.com_dense2.weight, tbs.com_dense2.bias, f32)
 
-    SAS_FUSED = bool(int(_os.environ.get('A4R_SAS_FUSED', '1')))       # 0: the multi-launch user tower (A/B runs)
-
     def _sas_fused_ok(self):
         """The one-launch-per-block kernels (a4r_sasrec.hip) serve the user tower when every block is the reference's default shape:
         64 wide, 2 heads x 32, d_inner 256, frozen dense weights and LayerNorms, a serial Houlsby or Compacter adapter after both
         sub-layers with bottleneck <= 32, no LoRA / Pfeiffer / parallel / K-Adapter.  Anything else keeps the multi-launch path."""
-        if not self.SAS_FUSED or self.sas_kads or not self.sas_blocks or self.Lseq - 1 > 32:
+        if self.sas_kads or not self.sas_blocks or self.Lseq - 1 > 32:
             return False
         for b in self.sas_blocks:
             if (b.H, getattr(b, 'Hv', b.H), b.nh, b.F, b.T) != (64, 64, 2, 256, torch.float32) or not b.causal or b.lora or b.train_dense:
@@ -918,17 +912,14 @@ class TransRecEngine:
             return False             # --fine_tune_to all: dW_i / dx1 of a TRAINABLE FFN use the derivative at storage precision, not the 8-bit form
         return self.q8_deriv and blk.T == torch.bfloat16 and getattr(blk, 'ffn_act', L.ACT_GELU) == L.ACT_GELU and blk.F % 16 == 0
 
-    Q8_TILED = _os.environ.get('A4R_Q8_TILED', '1') != '0'
-    VSKIP = _os.environ.get('A4R_VSKIP', '1') != '0'
-
     def _vskip(self, blk, which):
         """Sub-layer `which` of a post-LN block keeps y = LN(v) per layer (the tensor the next GEMM reads anyway) instead of v, and the fused
         adapter backward rebuilds xhat = (y - beta) / gamma: 62 MB less written per fused forward launch at B = 32.  Needs the one-launch
         kernels (bf16, serial Houlsby / Compacter placement), a frozen LayerNorm and |gamma| bounded away from 0."""
         ad, pl, ln = (blk.ad1, blk.pl1, blk.ln1) if which == '1' else (blk.ad2, blk.pl2, blk.ln2)
-        if not self.VSKIP or ad is None or pl != 'serial' or hasattr(blk, 'lnA') or blk.T != torch.bfloat16:
+        if ad is None or pl != 'serial' or hasattr(blk, 'lnA') or blk.T != torch.bfloat16:
             return False
-        if not (self.fuse_adapters and getattr(blk, 'Hv', blk.H) == blk.H and blk.H in (128, 256, 512, 768) and ad.dp == 64):
+        if not (getattr(blk, 'Hv', blk.H) == blk.H and blk.H in (128, 256, 512, 768) and ad.dp == 64):
             return False
         if ln.g_gamma is not None or ln.g_beta is not None:
             return False
@@ -943,7 +934,7 @@ class TransRecEngine:
     def _q8t(self, blk, M):
         """The 8-bit derivative tensor in the 256-tile kernel's own order (a4r_gemm_t.q8_tiled): only its writer (FFN-up) and its reader
         (the `* derivative` dgrad) ever touch it, and both see the same [M, F]."""
-        return self.Q8_TILED and self._q8(blk) and M % 256 == 0 and blk.F % 256 == 0
+        return self._q8(blk) and M % 256 == 0 and blk.F % 256 == 0
 
     def _block_bufs(self, tag, blk, M, shared, Mc=None):
         """Activation buffers of one block: `shared` => transient set reused by every block (inference).
@@ -1103,7 +1094,7 @@ class TransRecEngine:
 
     def _fuse(self, blk, ad, t):
         """The one-launch adapter kernels apply (bf16, bottleneck 64, a width they are instantiated for, no zero-padded block)."""
-        return self.fuse_adapters and getattr(blk, 'Hv', blk.H) == blk.H and L.adapter_ln_ok(t, ad.dp)
+        return getattr(blk, 'Hv', blk.H) == blk.H and L.adapter_ln_ok(t, ad.dp)
 
     # ---- one C call per layer (a4r_encoder_layer_fwd / _bwd, ABI 409): the launches below, sequenced by the library for the layers it covers --
     # bf16, short attention, serial Houlsby adapters on the one-launch kernels on both halves, frozen backbone.  Bit-identical to the per-launch path
@@ -1123,12 +1114,11 @@ class TransRecEngine:
         if any(d is not None and d.trainable for d in blk.qkv):
             return False
         for ad, pl, ln in ((blk.ad1, blk.pl1, blk.ln1), (blk.ad2, blk.pl2, blk.ln2)):
-            if ad is None or pl != 'serial' or ad.kind == 'compacter' or ad.virtual is not None or ad.dp != 64 or not self.fuse_adapters:
+            if ad is None or pl != 'serial' or ad.kind == 'compacter' or ad.virtual is not None or ad.dp != 64:
                 return False
             if ln.g_gamma is not None or ln.g_beta is not None:
                 return False
-            if backward and ad.g_wu is not None and not (TN2 and TN2_BIAS and not WGRAD_STREAM and ad.s_wu is None and ad.s_bd is None and ad.g_bu is not None
-                                                         and ad.g_bd is not None and self._bd_target(ad) is not None):
+            if backward and ad.g_wu is not None and (WGRAD_STREAM or ad.s_wu is not None or ad.s_bd is not None or ad.g_bu is None or ad.g_bd is None):
                 return False
         return True
 
@@ -1401,7 +1391,7 @@ class TransRecEngine:
         L.gemm_nt(x, sh['A'], t, bias=sh['ones'], M=M)                 # t[:, off .. off + r] per LoRA; t[:, ONES_COL] = 1 (bias gradients, see _Lora)
         L.gemm_nt(dqa, a.BT, dt, alpha=a.scaling, M=M)                 # dt = (dq B_q) s        (columns 0 .. r)
         L.gemm_nt(dqb, b.BT, dt, alpha=b.scaling, R1=dt, M=M)          #    + (dv B_v) s        (columns 16 .. 16 + r)
-        if TN2 and T == torch.bfloat16 and M % 64 == 0:
+        if T == torch.bfloat16 and M % 64 == 0:
             L.gemm_tn2(dqa, t, a.s_B, dqb, t, b.s_B, M=M)              # dB_. = d.^T t (the corner of its own rank columns is flushed)
         else:
             L.gemm_tn(dqa, t, a.s_B, M=M)
@@ -1434,17 +1424,17 @@ class TransRecEngine:
 
     def _bd_target(self, ad):
         """Where the down-projection's bias gradient accumulates (64 floats: the flat gradient or its zero-padded scratch), or None."""
-        if ad.g_bd is None or not FUSE_BD:
+        if ad.g_bd is None:
             return None
         return ad.s_bd if ad.s_bd is not None else ad.g_bd()
 
     def _tn2_bias_ok(self, ad, dv, M):
         """The adapter's two bias gradients can ride in its weight-gradient launch (a4r_gemm_tn2's xsum outputs: db_up = colsum(dv),
         db_down = colsum(dzp), from the bf16 tensors that launch reads anyway) instead of in the fused backward kernel's end-of-launch
-        flush -- 832 atomics from each of its 256 workgroups onto the same addresses, 6 - 9 us per launch (A4R_TN2_BIAS=0: the flush)."""
-        return (TN2_BIAS and TN2 and not (WGRAD_STREAM and self.WGRAD_SIDE_OK) and dv.dtype == torch.bfloat16 and M % 64 == 0
+        flush -- 832 atomics from each of its 256 workgroups onto the same addresses, 6 - 9 us per launch."""
+        return (not (WGRAD_STREAM and self.WGRAD_SIDE_OK) and dv.dtype == torch.bfloat16 and M % 64 == 0
                 and (ad.virtual is not None or ad.g_wu is not None) and ad.s_bd is None and ad.g_bu is not None and ad.g_bd is not None
-                and self._bd_target(ad) is not None and ad.dp == 64 and dv.shape[1] % 64 == 0)
+                and ad.dp == 64 and dv.shape[1] % 64 == 0)
 
     def _adapter_wgrads(self, ad, dv, z, dzp, down_in, M, bd_done=False, bias_in_tn2=False):
         """dW_up = dv^T z, dW_down = dzp^T down_in, db_down = colsum(dzp)  (db_up comes from ln_bwd's dbias; bd_done: the fused
@@ -1461,7 +1451,7 @@ class TransRecEngine:
             ev.record()
             with torch.cuda.stream(self._wstream):
                 self._wstream.wait_event(ev)
-                if TN2 and dv.dtype == torch.bfloat16:    # both products in one launch (32 against 2 x 21 us)
+                if dv.dtype == torch.bfloat16:    # both products in one launch (32 against 2 x 21 us)
                     L.gemm_tn2(dv, z, ad.g_wu(), dzp, down_in, ad.g_wd(), M=M)
                 else:
                     L.gemm_tn(dv, z, ad.g_wu(), M=M)
@@ -1481,7 +1471,7 @@ class TransRecEngine:
             assert dv.shape[1] * z.shape[1] == dzp.shape[1] * down_in.shape[1]
             L.gemm_tn2(dv, z, t_wu, dzp, down_in, t_wd, M=M, xsum1=ad.g_bu(), xsum2=ad.g_bd())
             return
-        if TN2 and dv.dtype == torch.bfloat16 and dv.shape[1] * z.shape[1] == dzp.shape[1] * down_in.shape[1] and M % 64 == 0:
+        if dv.dtype == torch.bfloat16 and dv.shape[1] * z.shape[1] == dzp.shape[1] * down_in.shape[1] and M % 64 == 0:
             L.gemm_tn2(dv, z, t_wu, dzp, down_in, t_wd, M=M)
         else:
             L.gemm_tn(dv, z, t_wu, M=M)
@@ -1823,12 +1813,13 @@ class TransRecEngine:
         16.97 -> 9.97 ms per step).  SASRec drops 1 of 42: the tower's large launches cost whole ROUNDS of 256-row tiles on the CUs, so 2.4 % fewer
         rows pay only where they remove a round (ViT-B/16 at 8 users: 259 -> 253 row panels = 4 -> 3 rounds of the H-wide GEMMs, 29.2 -> 26.9 ms); at
         the headline's 158 -> 154 panels (2 rounds either way) the step was 1.5 % SLOWER with the gather / scatter launches added: all slots stay."""
-        if _os.environ.get('A4R_SKIP_UNUSED_ITEMS', '1') == '0' or self.Lseq < 3:
+        mode = _skip_unused_items()
+        if mode == '0' or self.Lseq < 3:
             return None
         if self.arch == 'cpc':
             return B * (self.Lseq + 1)
         n_c = B * (2 * self.Lseq - 1)
-        if _os.environ.get('A4R_SKIP_UNUSED_ITEMS') == '2':           # (A/B runs: compact whatever the round count)
+        if mode == '2':           # (A/B runs: compact whatever the round count)
             return n_c
         ncu = 256
         if torch.device(self.dev).type == 'cuda':
@@ -1916,9 +1907,10 @@ class TransRecEngine:
         lm = log_mask.float().contiguous()
         n_items = n_full
         n_c = self._kept_rows(B)
+        skip = _skip_unused_items() != '0'
         kidx = None
         hm, self.host_log_mask = self.host_log_mask, None
-        if hm is not None and not hm.is_cuda and tuple(hm.shape) == (B, self.Lseq - 1) and _os.environ.get('A4R_SKIP_UNUSED_ITEMS', '1') != '0':
+        if hm is not None and not hm.is_cuda and tuple(hm.shape) == (B, self.Lseq - 1) and skip:
             kidx = self._kept_index(hm, B)
             if kidx is not None:
                 n_c = kidx[1]
@@ -1945,18 +1937,18 @@ class TransRecEngine:
         hmt, self.host_max_tokens = self.host_max_tokens, None
         S_step = self.S0
         if (hmt is not None and type(self) is TransRecEngine and not self.bert_kads and not self.prompt_n and self.S0 % 2 == 0 and news.dim() == 2
-                and news.dtype == torch.int64 and news.shape[1] == 2 * self.S0 and _os.environ.get('A4R_SKIP_UNUSED_ITEMS', '1') != '0'):
+                and news.dtype == torch.int64 and news.shape[1] == 2 * self.S0 and skip):
             S_step = min(self.S0, max(2, (int(hmt) + 1) // 2 * 2))
         self._set_S(S_step)
         # packed titles: every item runs on ITS OWN attended tokens (title lengths from the host copy of the rows, Model.forward), not on the batch's
         # longest title.  Needs prefix masks (a left-padded tokenizer or a mask with holes keeps the rectangular form), the MFMA attention kernels
-        # (head dim 32 / 64) and a frozen embedding (its backward is written for the rectangular layout).  A4R_PACK_TITLES=0: off (A/B runs).
+        # (head dim 32 / 64) and a frozen embedding (its backward is written for the rectangular layout).
         hl, self.host_lens = self.host_lens, None
         self._pk = None
         if (hl is not None and hmt is not None and S_step <= self.S0 and type(self) is TransRecEngine and not self.bert_kads and not self.prompt_n
                 and not self.train_emb and not self.fp8 and self.bert_blocks and self.bert_blocks[0].dh in (32, 64) and len(hl) == n_full
                 and not getattr(self.bert_blocks[0], 'long', False)             # (the long attention kernels take no offsets)
-                and _os.environ.get('A4R_PACK_TITLES', '1') != '0' and _os.environ.get('A4R_SKIP_UNUSED_ITEMS', '1') != '0'):
+                and skip):
             import numpy as np
             if kidx is not None:
                 rows_h = kidx[2]

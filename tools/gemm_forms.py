@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """a4r_gemm_nt on the training step's shapes WITH the epilogue forms the step uses (plain + bias, residual + dropout,
 GELU + derivative output, * saved derivative), us and TF/s per launch; `vendor` = torch.nn.functional.linear (hipBLASLt) on the
-plain form for orientation (measurement only: the product never calls it).  A4R_GEMM_BAND=0 / n selects the tile map.
+plain form for orientation (measurement only: the product never calls it).
 usage: python tools/gemm_forms.py [M=40448]"""
 import os
 import sys

@@ -1,6 +1,7 @@
 #!/usr/bin/env python
 """What the partial last round of a launch costs: the plain bf16 GEMM at M = 65 536 (256 row panels: whole rounds on 256 CUs) against the image
-tower's M = 66 304 (259 panels) for its four (N, K) shapes; A4R_GEMM_TAIL selects the largest short-tile height (0 = a whole extra round).
+tower's M = 66 304 (259 panels) for its four (N, K) shapes; an argument sets the largest short-tile height (a4r_gemm_tail_max; 0 = a whole extra round).
+usage: python tools/gemm_tail_cost.py [largest kp=3]
 
 CAVEAT (round 4): the launches are timed back to back and do not depend on each other, so the thin last round of one overlaps the first round of the next
 and "no tail" looks 5 - 10 % cheaper here than it is in the training step, where the consumer of a GEMM waits for its last tile: with the short-tile tail
@@ -21,6 +22,8 @@ def t_us(fn, n=20):
     return a.elapsed_time(b) / n * 1e3
 
 dev = torch.device('cuda:0')
+if len(sys.argv) > 1:
+    L.gemm_tail_max(int(sys.argv[1]))
 for N, K in ((768, 768), (2304, 768), (3072, 768), (768, 3072)):
     out = []
     for M in (65536, 66304, 40448):

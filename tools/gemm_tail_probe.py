@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Time of ONE short tile per CU against one full 256 x 256 tile per CU: launches that are all short tiles (N = 1024: 4 column panels x 64 short
-tiles of 32 kp rows = 256 workgroups) at kp = 1..7; run once with A4R_GEMM_TAIL=0 (the same rows as 8 kp full tiles on 32 kp CUs) and once with
-the default.  usage: python tools/gemm_tail_probe.py"""
+tiles of 32 kp rows = 256 workgroups) at kp = 1..7; run once with argument 0 (the same rows as 8 kp full tiles on 32 kp CUs) and once without (every height).
+usage: python tools/gemm_tail_probe.py [largest kp=7]"""
 import os
 import sys
 
@@ -27,8 +27,7 @@ def t_us(fn, n=30):
 
 
 L.gemm_variant(4)
-if os.environ.get('A4R_GEMM_TAIL') is None:
-    L.gemm_tail_max(7)          # every height (the default stops at kp = 3)
+L.gemm_tail_max(int(sys.argv[1]) if len(sys.argv) > 1 else 7)          # (7: every height; the default stops at kp = 3)
 g = torch.Generator(device=dev).manual_seed(3)
 for K in (768, 3072):
     for kp in (1, 2, 3, 4, 5, 6, 7, 8):

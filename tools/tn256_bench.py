@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """a4r_gemm_tn / a4r_gemm_tn_bias on the weight-gradient shapes of TRAINABLE backbone Linears (--fine_tune_to all / Pretraining): us and TF/s per
-product at M token rows.  A4R_TN256=0 python tools/tn256_bench.py = the 64-tile kernel on the same shapes; A4R_TN256_WGS=n: workgroups per launch.
-usage: python tools/tn256_bench.py [M=40448] [iters=30]"""
+product at M token rows.  A third argument 64 = the 64-tile kernel on the same shapes (a4r_gemm_variant(6)).
+usage: python tools/tn256_bench.py [M=40448] [iters=30] [tile=256]"""
 import os
 import sys
 
@@ -12,6 +12,7 @@ from adapter4rec_amd import _lib as L
 dev = torch.device('cuda:0')
 M = int(sys.argv[1]) if len(sys.argv) > 1 else 40448
 it = int(sys.argv[2]) if len(sys.argv) > 2 else 30
+tile = int(sys.argv[3]) if len(sys.argv) > 3 else 256
 
 
 def timed(fn):
@@ -27,7 +28,8 @@ def timed(fn):
     return a.elapsed_time(b) / it * 1e3
 
 
-print(f'A4R_TN256={os.environ.get("A4R_TN256", "1")} A4R_TN256_WGS={os.environ.get("A4R_TN256_WGS", "256")}')
+L.gemm_variant(6 if tile == 64 else 7)
+print(f'{tile}-tile weight-gradient kernel')
 for P, Q in ((768, 768), (3072, 768), (768, 3072), (2304, 768)):
     X = (torch.randn(M, P, device=dev) * 0.05).bfloat16()
     Y = torch.randn(M, Q, device=dev).bfloat16()

@@ -50,4 +50,4 @@ for _ in range(30):
 b.record()
 torch.cuda.synchronize()
 us = a.elapsed_time(b) / 30 * 1e3
-print(f'gemm_tn2 + column sums M={M}: {us:6.1f} us  {M * (768 + 64) * 2 * 2 / us / 1e6:5.2f} TB/s   (A4R_TN2_WGS={os.environ.get("A4R_TN2_WGS", "384")})')
+print(f'gemm_tn2 + column sums M={M}: {us:6.1f} us  {M * (768 + 64) * 2 * 2 / us / 1e6:5.2f} TB/s')
