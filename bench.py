@@ -16,10 +16,14 @@ loss.backward() (native backward straight into the flat gradient buffer + ONE RC
 `--gpus N` with N > 1 and no launcher environment starts N ranks itself (one process per GPU, torch.distributed.run on
 127.0.0.1) BEFORE anything touches the GPU; under a launcher (WORLD_SIZE set) it is one of the ranks.  It exits non-zero if
 it ends up with a rank count other than N.  The JSON line carries `rccl_ranks` (the result of an actual all-reduce of ones),
-the all-reduce payload and its measured time.
-Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel (the bf16 MFMA GEMM), measured with HIP events
-in an instrumented pass run after the timed region; `cpu_baseline` times the CPU oracle (oracle/ref_cpu.py) on a
-bounded sample of the same workload on the host cores.
+and the all-reduce payload.
+Prints ONE JSON line (rank 0).
+
+A plain run does what the headline figure needs and no more: set-up, warm-up, the timed steps, --dump-outputs, the line.  Everything
+else this file measures or checks runs behind `--full`, after the timed region, and is null in a plain run's line: `roofline` for the
+dominant kernel (the bf16 MFMA GEMM), measured with HIP events in an instrumented pass; `cpu_baseline`, which times the CPU oracle
+(oracle/ref_cpu.py) on a bounded sample of the same workload on the host cores and compares the HIP path with it;
+`host_enqueue_ms_per_step` (a burst of steps from an idle device); `allreduce_us` (the gradient exchange on its own, --gpus > 1).
 """
 import argparse
 import json
@@ -453,12 +457,16 @@ def main():
     ap.add_argument('--dtype', default='bf16', choices=['bf16', 'fp32', 'fp8'],
                     help='fp8: bf16 storage + OCP e4m3 operands (block-scaled MFMA rate) for the frozen encoder\'s qkv / attention-output / FFN forward GEMMs and the FFN dgrads, '
                          'text and image towers (BASELINE.json quotes the headline in bf16: the default)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, also run the legs that the headline figure does not need: the instrumented roofline pass, the CPU-oracle '
+                         'baseline and its comparison with the HIP path, the host-enqueue burst and (--gpus > 1) the all-reduce on its own.  Off by '
+                         'default: a plain run sets up, warms up, times the steps and prints the line with those fields null')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: leave out the CPU-oracle leg')
     ap.add_argument('--host-images', action='store_true',
                     help='image workloads: ALSO time the step with its uint8 batch coming from PINNED HOST memory every step (H2D on a copy stream, '
                          'overlapped with the previous step: the LMDB -> GPU pipeline of SURVEY 8(d)); reported next to `value`, which stays the '
                          'HBM-resident figure')
-    ap.add_argument('--no-roofline', action='store_true')
+    ap.add_argument('--no-roofline', action='store_true', help='with --full: leave out the instrumented roofline pass')
     ap.add_argument('--ragged-histories', action='store_true',
                     help='NOT the canonical benchmark: user histories of 2 .. 21 items (left-padded with item 0 / zero images), log_mask handed over on the host; '
                          'the engine does not encode the pad slots')
@@ -618,19 +626,21 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    # what the LAST timed step returned, taken before the burst / instrumented steps below move the parameters on (outside the timed region)
+    # what the LAST timed step returned, taken before the --full burst / instrumented steps below move the parameters on (outside the timed region)
     dumped = dump_outputs(a.dump_outputs, model, loss) if (a.dump_outputs and rank == 0) else None
     if dumped is not None:
         dumped['last_timed_step_from'] = ('the seeded trainable state: parameters restored, Adam moments and step count reset, once inside the '
                                           'timed region before the last timed step; the other timed steps train on as without --dump-outputs')
-    # host time to ENQUEUE a step (nothing in a step waits for the device): a short burst behind the timed region, from an idle device -- over the K timed
-    # steps the host is throttled by the full launch queue and its clock only mirrors the device's.  host >= device means the step is host-bound.
-    nb = min(8, a.steps)
-    t1 = time.perf_counter()
-    for i in range(nb):
-        step(a.warmup + a.steps + i)
-    dt_host = (time.perf_counter() - t1) / nb * a.steps
-    torch.cuda.synchronize()
+    # --full: host time to ENQUEUE a step (nothing in a step waits for the device): a short burst behind the timed region, from an idle device -- over the
+    # K timed steps the host is throttled by the full launch queue and its clock only mirrors the device's.  host >= device means the step is host-bound.
+    host_ms = None
+    if a.full:
+        nb = min(8, a.steps)
+        t1 = time.perf_counter()
+        for i in range(nb):
+            step(a.warmup + a.steps + i)
+        host_ms = round((time.perf_counter() - t1) / nb * 1e3, 3)
+        torch.cuda.synchronize()
     rank_ms = [round(dt / a.steps * 1e3, 3)]
     if world > 1:
         # every rank's own clock over the same K steps (they end at a barrier, so the spread is what each rank measured between ITS
@@ -649,7 +659,7 @@ def main():
         raise SystemExit(f'bench.py: the replicas left lock-step: {lock}')
 
     ar_us = None
-    if world > 1:                                              # the exchange step on its own: 20 all-reduces of the flat gradient buffer
+    if world > 1 and a.full:                                   # the exchange step on its own: 20 all-reduces of the flat gradient buffer
         scratch = torch.zeros_like(eng.flat_g)
         for _ in range(3):
             ddp.average_(scratch)
@@ -733,7 +743,7 @@ def main():
                     'with_over_without': round((world * a.batch * K / dth) / (world * a.batch * a.steps / dt), 4)}
 
     roof = None
-    if rank == 0 and not a.no_roofline:
+    if rank == 0 and a.full and not a.no_roofline:
         import adapter4rec_amd.engine as E
         side, E.WGRAD_STREAM = E.WGRAD_STREAM, False             # single stream here: an event pair would also time the wait for CUs that
         with GemmProbe(E.L) as probe:                            # side-stream weight-gradient kernels still hold when a GEMM is launched
@@ -813,7 +823,7 @@ def main():
             print(json.dumps(shapes, indent=1), file=sys.stderr)
 
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline and wl == 'bert_houlsby':
+    if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline and wl == 'bert_houlsby':
         cpu = cpu_baseline(device)
 
     if rank == 0:
@@ -825,7 +835,7 @@ def main():
                        'mae_pretrain': 'user-sequences/sec, seq_len=23 MAE+SASRec full fine-tuning (Pretraining/CV)'}[wl],
             'value': round(users / dt, 2),
             'unit': 'user-sequences/sec', 'n_gpus': world, 'steps': a.steps, 'warmup': a.warmup,
-            'ms_per_step': round(dt / a.steps * 1e3, 3), 'host_enqueue_ms_per_step': round(dt_host / a.steps * 1e3, 3), 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
+            'ms_per_step': round(dt / a.steps * 1e3, 3), 'host_enqueue_ms_per_step': host_ms, 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
             'dtype': a.dtype, 'data': WORKLOADS[wl][3] + (' -- RAGGED histories of 2..21 items (not the canonical benchmark)' if getattr(a, 'ragged_histories', False) else '') + (' -- SHORT titles of 6..20 tokens (not the canonical benchmark)' if getattr(a, 'short_titles', False) else '')
                     + (' -- REAL-SHAPED: title lengths ~ the 20 373 Adressa titles, history lengths ~ the 21 153 Amazon users the reference ships (tests/golden/real_shapes.json)' if getattr(a, 'real_shaped', False) else ''),
             'config': {'workload': WORKLOADS[wl][2], 'baseline_config': WORKLOADS[wl][0] + (' in bf16 (run with --dtype fp8 for its fp8 encoder)' if wl == 'mae_compacter' and a.dtype != 'fp8' else ''),

@@ -38,6 +38,15 @@ def test_single_rank_needs_no_launcher():
     assert len(lines) == 1 and lines[0]['n_gpus'] == 1 and lines[0]['rccl_ranks'] == 1
 
 
+def test_full_is_accepted_by_the_launch_path():
+    """--full (the legs beyond the headline figure) is an option of every run, the self-launched ranks included: it reaches them on their command line."""
+    for gpus in ('1', '2'):
+        r = run(['--gpus', gpus, '--steps', '1', '--warmup', '0', '--full'])
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = json_lines(r.stdout)
+        assert len(lines) == 1 and lines[0]['n_gpus'] == int(gpus), r.stdout
+
+
 def test_rank_count_mismatch_is_an_error():
     """Under a launcher that gives fewer ranks than --gpus the run must fail instead of printing n_gpus of a job that did not run."""
     r = run(['--gpus', '4'], extra_env=dict(WORLD_SIZE='1', RANK='0', LOCAL_RANK='0'))
@@ -126,12 +135,29 @@ def test_bench_dump_outputs_of_the_last_timed_step(tmp_path):
 
 
 @pytest.mark.gpu
+def test_plain_run_leaves_the_full_legs_out():
+    """Without --full a run ends with its timed steps: the headline fields are there, and what only --full measures (roofline pass, CPU-oracle
+    baseline, host-enqueue burst) is null in the line instead of being run."""
+    env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '2', '--batch', '8'],
+                       env=env, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = json_lines(r.stdout)
+    assert len(lines) == 1, r.stdout
+    d = lines[0]
+    assert d['value'] > 0 and d['ms_per_step'] > 0 and d['unit'] == 'user-sequences/sec' and d['higher_is_better'] is True and d['dtype'] == 'bf16'
+    assert abs(d['value'] - 8 / (d['ms_per_step'] * 1e-3)) <= 1e-3 * d['value']
+    assert d['roofline'] is None and d['cpu_baseline'] is None and d['host_enqueue_ms_per_step'] is None and d['allreduce_us'] is None
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize('dump', [False, True])
 def test_bench_host_images_leg(tmp_path, dump):
-    """--workload vit_lora --host-images (the pinned-host-memory leg after the timed region) with the roofline pass after it, with and without
-    --dump-outputs: one JSON line carrying both."""
+    """--workload vit_lora --host-images (the pinned-host-memory leg after the timed region) with --full's roofline pass after it, with and
+    without --dump-outputs: one JSON line carrying both."""
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
-    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--workload', 'vit_lora', '--host-images', '--steps', '2', '--warmup', '1', '--no-cpu-baseline']
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--workload', 'vit_lora', '--host-images', '--steps', '2', '--warmup', '1', '--full',
+           '--no-cpu-baseline']
     if dump:
         cmd += ['--dump-outputs', str(tmp_path / 'dump')]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)

@@ -148,13 +148,13 @@ def test_one_rank_rccl_chunked_exchange_equals_single_allreduce(tmp_path):
 def test_bench_two_ranks_oversubscribed_json_line():
     """bench.py --gpus 2 end to end on the one GPU (A4R_BENCH_OVERSUBSCRIBE=1: both ranks on cuda:0, gloo -- RCCL refuses duplicate devices):
     self-launch, rendezvous on 127.0.0.1, the flat-gradient exchange on device tensors inside the timed public path, ONE JSON line from rank 0
-    with the multi-rank fields the first SCALE record will be read by (VERDICT r3 task 6c)."""
+    with the multi-rank fields the first SCALE record will be read by (VERDICT r3 task 6c); --full for the all-reduce timed on its own."""
     import json
     import subprocess
     root = os.path.dirname(HERE)
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
     env.update(A4R_BENCH_OVERSUBSCRIBE='1', A4R_BENCH_BACKEND='gloo')
-    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '4', '--warmup', '2', '--batch', '8', '--no-roofline'],
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '4', '--warmup', '2', '--batch', '8', '--full', '--no-roofline'],
                        env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [json.loads(l) for l in r.stdout.splitlines() if l.startswith('{')]

@@ -4,6 +4,6 @@
 base=${1:-tools/_ab/liba4r_hip_base.so}; rounds=${2:-3}
 for i in $(seq $rounds); do
   for lib in "$base" ""; do
-    A4R_LIB_PATH=$lib timeout 300 python bench.py --no-cpu-baseline --steps 30 ${BENCH_ARGS} 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('${lib:-current}', d['value'], d['ms_per_step'], d['roofline']['achieved'], d['roofline']['all_gemm_tflops'])"
+    A4R_LIB_PATH=$lib timeout 300 python bench.py --full --no-cpu-baseline --steps 30 ${BENCH_ARGS} 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('${lib:-current}', d['value'], d['ms_per_step'], d['roofline']['achieved'], d['roofline']['all_gemm_tflops'])"
   done
 done
