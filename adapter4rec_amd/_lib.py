@@ -30,11 +30,14 @@ EXPORTS = [
     'a4r_sasrec_block_fwd', 'a4r_sasrec_block_bwd', 'a4r_scatter_rows_fill', 'a4r_attn_long_fwd', 'a4r_attn_long_bwd', 'a4r_patchify', 'a4r_vit_assemble', 'a4r_resample_u8', 'a4r_embed_bwd', 'a4r_mae_keep_indices',
     'a4r_encoder_layer_fwd', 'a4r_encoder_layer_bwd', 'a4r_id_index', 'a4r_id_index_ws_ints', 'a4r_id_grad_sum',
     'a4r_topk_items', 'a4r_grad_sumsq', 'a4r_adamw_step',
+    'a4r_score_ce_ranges', 'a4r_score_ce_fwd', 'a4r_score_ce_bwd_rows', 'a4r_score_ce_bwd_items',
 ]
 ID_SUM_CHUNK = 16          # A4R_ID_SUM_CHUNK (include/a4r.h)
 TOPK_MAX_K = 256           # A4R_TOPK_MAX_K (include/a4r.h)
 TOPK_E = (64, 128, 256, 512)
 GRAD_NORM_PARTS = 1024     # A4R_GRAD_NORM_PARTS (include/a4r.h)
+SCORE_CE_E = TOPK_E         # table widths of the cross-entropy head (a4r_score_ce_*)
+SCORE_CE_MAX_RANGES = 32   # A4R_SCORE_CE_MAX_RANGES (include/a4r.h)
 
 
 class GemmArgs(C.Structure):
@@ -111,9 +114,14 @@ def lib():
                 f'{LIB_PATH} not found: build it with `python -c "import __graft_entry__ as g; g.build()"` '
                 '(hipcc --offload-arch=gfx950).  adapter4rec_amd has no CPU / PyTorch fallback.')
         _lib = C.CDLL(LIB_PATH)
+        missing = [name for name in EXPORTS if not hasattr(_lib, name)]
+        if missing:                   # a build from before an entry point was added (additions keep the ABI number: no argument list changes)
+            _lib = None
+            raise RuntimeError(f'{LIB_PATH} lacks {", ".join(missing)}: rebuild it (make -C adapter4rec_amd/csrc)')
         for name in EXPORTS:
             getattr(_lib, name).restype = C.c_int
-        _lib.a4r_topk_ws_bytes.restype = C.c_size_t        # (the one size_t-valued export; not in EXPORTS, whose entries return a status)
+        _lib.a4r_topk_ws_bytes.restype = C.c_size_t        # (the size_t-valued exports; not in EXPORTS, whose entries return a status)
+        _lib.a4r_score_ce_ws_bytes.restype = C.c_size_t
         got = _lib.a4r_version()
         if got != ABI_VERSION:        # an older A/B build has every export but other argument lists: calling it would pass shifted pointers
             _lib = None
@@ -680,6 +688,71 @@ def score_bce_bwd(emb, prec, log_mask, pos, neg, loss_ws, loss_scale, d_prec, d_
     assert scale_dev is None or (scale_dev.dtype == torch.float32 and scale_dev.numel() == 1)
     _check(lib().a4r_score_bce_bwd(_stream(), _p(emb), _p(prec), _p(log_mask), _p(pos), _p(neg), _p(loss_ws), C.c_float(loss_scale), _p(scale_dev),
                                    _p(d_prec), _p(d_emb), C.c_int(B), C.c_int(L), C.c_int(E), C.c_int(int(cpc))), 'a4r_score_bce_bwd')
+
+
+def score_ce_ranges(R, N1):
+    """The library's own item-range count for R rows against an [N1, E] table (a host-side query): <= SCORE_CE_MAX_RANGES and <= the table's
+    16-item tiles."""
+    k = int(lib().a4r_score_ce_ranges(C.c_int(R), C.c_int(N1)))
+    if k < 1:
+        raise ValueError(f'score_ce_ranges: R = {R} rows and N1 = {N1} table rows (row 0 = the pad item): need R >= 1, N1 >= 2')
+    return k
+
+
+def score_ce_ws_bytes(R, N1, E, ranges=0):
+    """Bytes of the workspace a4r_score_ce_fwd / _bwd_rows share (a host-side query); ranges 0 = the library's choice.  0 for arguments the
+    kernels refuse.  Independent of N1 at a fixed range count: nothing of size rows x items exists."""
+    return int(lib().a4r_score_ce_ws_bytes(C.c_int(R), C.c_int(N1), C.c_int(E), C.c_int(ranges)))
+
+
+def _score_ce_ws(prec, R, N1, E, ranges, ws):
+    if ws is None:
+        ws = torch.empty(max(score_ce_ws_bytes(R, N1, E, ranges), 16), dtype=torch.uint8, device=prec.device)
+    assert ws.is_contiguous() and ws.numel() * ws.element_size() >= score_ce_ws_bytes(R, N1, E, ranges)
+    return ws
+
+
+def _score_ce_check(prec, table, tgt, log_mask, R):
+    require_gpu(prec, table, tgt, log_mask)
+    assert prec.dim() == 2 and table.dim() == 2 and prec.dtype == torch.float32 and table.dtype == torch.float32
+    assert prec.is_contiguous() and table.is_contiguous() and prec.shape[1] == table.shape[1] and prec.shape[0] >= R
+    assert tgt.dtype == torch.int32 and tgt.is_contiguous() and tgt.numel() >= R
+    assert log_mask.dtype == torch.float32 and log_mask.is_contiguous() and log_mask.numel() >= R
+
+
+def score_ce_fwd(prec, table, tgt, log_mask, lse, s_tgt, loss_ws, R, ranges=0, ws=None):
+    """a4r_score_ce_fwd: full-softmax cross-entropy of the first R rows of prec [>= R, E] against the items 1 .. N1-1 of table [N1, E] (include/a4r.h).
+    tgt int32 [R], log_mask fp32 [R]; lse, s_tgt fp32 [R] and loss_ws fp32 [4] (loss, sum, trained rows) are overwritten.  ws: scratch of
+    score_ce_ws_bytes bytes (allocated here when None).  The shape arguments go to the library as they are: it answers an unsupported width, R < 1,
+    N1 < 2 or ranges outside 0 .. 32 with its invalid-argument status before any launch."""
+    _score_ce_check(prec, table, tgt, log_mask, max(R, 0))
+    require_gpu(lse, s_tgt, loss_ws)
+    assert all(t.dtype == torch.float32 and t.is_contiguous() for t in (lse, s_tgt, loss_ws)) and lse.numel() >= R and s_tgt.numel() >= R and loss_ws.numel() >= 4
+    N1, E = table.shape
+    ws = _score_ce_ws(prec, R, N1, E, ranges, ws)
+    _check(lib().a4r_score_ce_fwd(_stream(), _p(prec), _p(table), _p(tgt), _p(log_mask), _p(lse), _p(s_tgt), _p(loss_ws), _p(ws),
+                                  C.c_int(R), C.c_int(N1), C.c_int(E), C.c_int(ranges)), 'a4r_score_ce_fwd')
+
+
+def score_ce_bwd(prec, table, tgt, log_mask, lse, loss_ws, loss_scale, d_prec, d_table, R, ranges=0, scale_dev=None, ws=None):
+    """The two backward launches of the cross-entropy head (include/a4r.h), both recomputing the scores from prec, table and the forward's lse:
+    a4r_score_ce_bwd_rows overwrites d_prec [>= R, E] (contiguous; None: skipped), a4r_score_ce_bwd_items ADDS into d_table [N1, >= E] (row 0
+    untouched; None: skipped, a frozen table).  The incoming gradient is loss_scale x scale_dev[0] (scale_dev: a one-element fp32 device tensor)."""
+    _score_ce_check(prec, table, tgt, log_mask, max(R, 0))
+    require_gpu(lse, loss_ws, d_prec, d_table, scale_dev)
+    assert scale_dev is None or (scale_dev.dtype == torch.float32 and scale_dev.numel() == 1)
+    N1, E = table.shape
+    if d_prec is not None:
+        assert d_prec.dtype == torch.float32 and d_prec.is_contiguous() and d_prec.shape[1] == E and d_prec.shape[0] >= R
+        ws = _score_ce_ws(prec, R, N1, E, ranges, ws)
+        _check(lib().a4r_score_ce_bwd_rows(_stream(), _p(prec), _p(table), _p(tgt), _p(log_mask), _p(lse), _p(loss_ws), C.c_float(loss_scale),
+                                           _p(scale_dev), _p(d_prec), _p(ws), C.c_int(R), C.c_int(N1), C.c_int(E), C.c_int(ranges)),
+               'a4r_score_ce_bwd_rows')
+    if d_table is not None:
+        assert d_table.dtype == torch.float32 and d_table.dim() == 2 and d_table.stride(1) == 1 and d_table.shape[0] >= N1
+        _check(lib().a4r_score_ce_bwd_items(_stream(), _p(prec), _p(table), _p(tgt), _p(log_mask), _p(lse), _p(loss_ws), C.c_float(loss_scale),
+                                            _p(scale_dev), _p(d_table), C.c_int(d_table.stride(0)), C.c_int(R), C.c_int(N1), C.c_int(E)),
+               'a4r_score_ce_bwd_items')
 
 
 def emb_grad_add_inputs(d_in, d_emb, B, L, E):

@@ -2141,8 +2141,7 @@ class TransRecEngine:
         Ip = pad_to(n_full, 128)
         d_prec = self._buf_tail0('d_prec', Mu, E, torch.float32, B * Tn)     # score_bce_bwd writes the real rows only
         d_emb = self._buf_tail0('d_emb', Ip, E, torch.float32, n_full)
-        L.score_bce_bwd(c['emb'], c['prec'], c['lm'], c['pos'], c['neg'], c['ws'], 1.0, d_prec, d_emb, B, self.Lseq, E, self.arch == 'cpc',
-                        scale_dev=grad_out)
+        self._head_backward(c, grad_out, d_prec, d_emb, B)
         # SASRec blocks, last to first
         dx = d_prec
         dlast = None
@@ -2182,6 +2181,11 @@ class TransRecEngine:
         L.emb_grad_add_inputs(d_in, d_emb, B, self.Lseq, E)
         self._exchange('user')
         return c, target, d_emb
+
+    def _head_backward(self, c, grad_out, d_prec, d_emb, B):
+        """The scoring head's backward: d_prec (the user tower's output gradient) and the target-side rows of d_emb."""
+        L.score_bce_bwd(c['emb'], c['prec'], c['lm'], c['pos'], c['neg'], c['ws'], 1.0, d_prec, d_emb, B, self.Lseq, self.E, self.arch == 'cpc',
+                        scale_dev=grad_out)
 
     def _backward_finish(self, target, into_flat_grad, as_list):
         """After the item tower's backward: side-stream joins, scratch corners, virtual adapters; the per-parameter list (autograd path)."""

@@ -2,7 +2,8 @@
 user tower fed by a learned item-ID table instead of an item encoder.
 
 Forward: a4r_id_index turns the batch's slot ids into the int32 rows a4r_rows_idx_copy gathers the table with, plus the inverted index (every
-distinct id's slots in slot order); the head and the user tower are TransRecEngine's.  Backward: TransRecEngine's head + user-tower half,
+distinct id's slots in slot order); the user tower is TransRecEngine's, the head its BCE head (--loss bce) or the softmax cross-entropy over the
+whole table (--loss ce: a4r_score_ce_*, whose item-side gradient is dense and goes straight into the table's gradient).  Backward: TransRecEngine's head + user-tower half,
 then a4r_id_grad_sum adds each listed row's gradient into the table's slice of the flat gradient buffer in a fixed order (no float atomics:
 the table gradient is a function of the batch alone).  The table lives in flat_p as fp32 and the forward reads that parameter view directly.
 """
@@ -12,11 +13,25 @@ from . import _lib as L
 from .engine import TransRecEngine, pad_to
 
 
+def loss_flag(args, arch, use_modal):
+    """args.loss ('bce' when absent) after the checks of --loss ce: it needs the ID table as its candidate set and the SASRec user tower."""
+    loss = getattr(args, 'loss', 'bce') or 'bce'
+    if loss not in ('bce', 'ce'):
+        raise ValueError(f"--loss must be 'bce' or 'ce', got {loss!r}")
+    if loss == 'ce' and use_modal:
+        raise NotImplementedError('--loss ce with an item encoder (--item_tower modal): the full-softmax head needs the candidate set to be '
+                                  'the ID table itself (--item_tower id)')
+    if loss == 'ce' and arch == 'cpc':
+        raise NotImplementedError('--loss ce with --arch cpc: the full-softmax head is built for the SASRec user tower only')
+    return loss
+
+
 class IdRecEngine(TransRecEngine):
 
     def __init__(self, model, args, arch='sasrec', dtype='bf16', phm_owner=None):
         if dtype == 'fp8':
             raise NotImplementedError('--compute_dtype fp8 with --item_tower id: the ID tower has no backbone GEMM to quantise')
+        self.loss = loss_flag(args, arch, False)
         super().__init__(model, args, arch=arch, dtype=dtype, phm_owner=phm_owner)
         self._err_pending, self._err_free = [], []           # (pinned host word, event) per step not yet checked; spare words
 
@@ -25,6 +40,8 @@ class IdRecEngine(TransRecEngine):
         self.item_num = w.shape[0] - 1
         if w.shape[1] != self.E or self.E % 4:
             raise NotImplementedError(f'ID table width {w.shape[1]} (embedding_dim {self.E}, a multiple of 4)')
+        if self.loss == 'ce' and self.E not in L.SCORE_CE_E:
+            raise NotImplementedError(f'--loss ce with embedding_dim {self.E}: a4r_score_ce_* serves the widths {L.SCORE_CE_E}')
         self.H = self.E
         self.bert_blocks, self.bert_kads, self.cls_only, self.train_emb, self.prompt_n = [], [], False, False, 0
         self.table = w.data if w.requires_grad else self._f32(w)          # (trainable: the fp32 view into flat_p, never repacked)
@@ -129,15 +146,47 @@ class IdRecEngine(TransRecEngine):
         xin = self._buf('sxin', Mu, E, torch.float32)
         L.take_inputs(emb, xin, B, self.Lseq, E)
         prec, Mu = self._user_forward(xin, lm, B, train, seed, self._saved_sas)
+        ws = self._buf('lossws', 1, 4, torch.float32)
+        if self.loss == 'ce':
+            return self._ce_forward(B, n_full, Mu, seed, train, lm, emb, prec, xin, ws, ix)
         pos = self._buf('pos', B, self.Lseq - 1, torch.float32)
         neg = self._buf('neg', B, self.Lseq - 1, torch.float32)
-        ws = self._buf('lossws', 1, 4, torch.float32)
         L.zero(ws)
         L.score_bce_fwd(emb, prec, lm, pos, neg, ws, B, self.Lseq, E, self.arch == 'cpc')
         self._post_err(ix['err'])
         self._ctx = dict(B=B, n_items=n_full, n_full=n_full, M=0, Mu=Mu, seed=seed, train=train, lm=lm, emb=emb, prec=prec, xin=xin, pos=pos,
                          neg=neg, ws=ws, saved_s=self._saved_sas, ix=ix)
         return ws[0, 0].clone()
+
+    # ------------------------------------------------------------------ --loss ce: softmax cross-entropy over the whole table
+    def _ce_ws(self, R):
+        """The scratch a4r_score_ce_fwd and _bwd_rows share (ranges x R x E floats, whatever the table's size)."""
+        return self._buf('ce.ws', L.score_ce_ws_bytes(R, self.item_num + 1, self.E), 1, torch.uint8).view(-1)
+
+    def _ce_forward(self, B, n_full, Mu, seed, train, lm, emb, prec, xin, ws, ix):
+        """The head of train_forward under --loss ce: row (b, t) is trained against every item of the table with the positive id of position
+        t + 1 as its class (a4r_score_ce_fwd); the batch's sampled negatives are not read.  rows holds the range-checked slot ids."""
+        T = self.Lseq - 1
+        R = B * T
+        tgt = self._buf('ce.tgt', R, 1, torch.int32).view(-1)
+        tgt.view(B, T).copy_(ix['rows'][:n_full].view(B, self.Lseq, 2)[:, 1:, 0])
+        lse = self._buf('ce.lse', R, 1, torch.float32).view(-1)
+        s_tgt = self._buf('ce.s_tgt', R, 1, torch.float32).view(-1)
+        L.score_ce_fwd(prec, self.table, tgt, lm.view(-1), lse, s_tgt, ws.view(-1), R, ws=self._ce_ws(R))
+        self._post_err(ix['err'])
+        self._ctx = dict(B=B, n_items=n_full, n_full=n_full, M=0, Mu=Mu, seed=seed, train=train, lm=lm, emb=emb, prec=prec, xin=xin, tgt=tgt,
+                         lse=lse, ws=ws, saved_s=self._saved_sas, ix=ix)
+        return ws[0, 0].clone()
+
+    def _head_backward(self, c, grad_out, d_prec, d_emb, B):
+        """--loss ce: d_prec from a4r_score_ce_bwd_rows; the target side of the head goes straight into the table's gradient (a4r_score_ce_bwd_items
+        adds into the current gradient target, every row but row 0), so d_emb starts at zero and carries the user tower's input gradient alone."""
+        if self.loss != 'ce':
+            return super()._head_backward(c, grad_out, d_prec, d_emb, B)
+        R = B * (self.Lseq - 1)
+        L.zero(d_emb)
+        L.score_ce_bwd(c['prec'], self.table, c['tgt'], c['lm'].view(-1), c['lse'], c['ws'].view(-1), 1.0, d_prec,
+                       self.g_table() if self.g_table is not None else None, R, scale_dev=grad_out, ws=self._ce_ws(R))
 
     def train_backward(self, grad_out=None, into_flat_grad=False, as_list=True):
         """The shared head + user-tower backward (TransRecEngine._head_user_backward), then the table's gradient: a4r_id_grad_sum of the

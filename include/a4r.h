@@ -500,6 +500,34 @@ size_t a4r_topk_ws_bytes(int U, int N1, int K);
 int a4r_topk_items(void* stream, const float* prec, const float* item_emb, const int32_t* excl_ptr, const int32_t* excl_idx,
                    int32_t* ids, float* scores, void* ws, int U, int N1, int E, int K);
 
+/* Full-softmax cross-entropy head of the ID tower (--loss ce; new exports, ABI 411 kept: no existing argument list changes): rows r < R = (user, position) with vectors prec (fp32 [R, E]) against the whole
+ * item table (fp32 [N1, E]; row 0 is the pad row and never a candidate), s[r, i] = <prec[r], table[i]> formed as a4r_topk_items forms it, without
+ * materialising [R, N1].  tgt int32 [R] (the positive item of the row), log_mask fp32 [R].
+ *   trained(r) = log_mask[r] != 0 and 1 <= tgt[r] < N1 (0, and any id outside the table, = row not trained); count = trained rows, counted on the device
+ *   fwd:  lse[r] = log sum_{i = 1 .. N1-1} exp s[r, i] and s_tgt[r] = s[r, tgt[r]] (0 where tgt[r] is no item) for EVERY row; loss_ws (4 floats,
+ *         overwritten): [0] loss = sum over trained rows of (lse - s_tgt) / count, [1] that sum, [2] count.  count == 0: loss 0.
+ *   bwd_rows:  d_prec [R, E] = g / count x (sum_i p[r, i] table[i] - table[tgt[r]]), p = exp(s - lse); exact zeros for rows not trained (overwrites).
+ *   bwd_items: d_table[i, :] += g / count x sum over trained r of (p[r, i] - [i == tgt[r]]) prec[r], i = 1 .. N1-1 (fp32 [N1, ldg]; row 0 is never
+ *         written; every row is written once, by one wave; count == 0 or g == 0: nothing is written).
+ *   g = loss_scale x (*loss_scale_dev if non-null), as a4r_score_bce_bwd.  Both backward launches recompute the scores from prec, table and lse.
+ * ranges: item ranges the table is cut into per 16-row tile (grid y), 1 .. A4R_SCORE_CE_MAX_RANGES, or 0 = a4r_score_ce_ranges(R, N1), the library's
+ * choice from the CU count (never more than the 16-item tiles of the table); a range may hold no item.  fwd and bwd_rows each run a second, small
+ * launch that folds the ranges in range order.  ws: a4r_score_ce_ws_bytes(R, N1, E, ranges) bytes of device scratch, 16-byte aligned, shared by
+ * fwd and bwd_rows (contents need not be kept): ranges x R x E floats, independent of N1.  No float atomics: the same inputs give the same bits.
+ * E in {64, 128, 256, 512}, R >= 1, N1 >= 2, ranges in 0 .. 32, prec and table 16-byte aligned; anything else returns A4R_EINVAL before any launch
+ * (a4r_score_ce_ws_bytes returns 0). */
+#define A4R_SCORE_CE_MAX_RANGES 32
+size_t a4r_score_ce_ws_bytes(int R, int N1, int E, int ranges);
+int a4r_score_ce_ranges(int R, int N1);
+int a4r_score_ce_fwd(void* stream, const float* prec, const float* table, const int32_t* tgt, const float* log_mask, float* lse,
+                     float* s_tgt, float* loss_ws, void* ws, int R, int N1, int E, int ranges);
+int a4r_score_ce_bwd_rows(void* stream, const float* prec, const float* table, const int32_t* tgt, const float* log_mask,
+                          const float* lse, const float* loss_ws, float loss_scale, const float* loss_scale_dev, float* d_prec,
+                          void* ws, int R, int N1, int E, int ranges);
+int a4r_score_ce_bwd_items(void* stream, const float* prec, const float* table, const int32_t* tgt, const float* log_mask,
+                           const float* lse, const float* loss_ws, float loss_scale, const float* loss_scale_dev, float* d_table,
+                           int ldg, int R, int N1, int E);
+
 /* The learned item-ID table of the IDRec baseline (ABI 410; Downstream/CV/model/model.py: nn.Embedding(item_num + 1, E, padding_idx=0), fed the flat
  * slot ids of a batch).  a4r_id_index, once per step: rows[i] = ids[i] when 0 <= ids[i] <= item_num, else 0 and counted in *err (overwritten: the
  * number of such slots in this call) -- rows is what a4r_rows_idx_copy gathers the table with.  The inverted index in CSR form: *n_uniq distinct

@@ -2,12 +2,15 @@
 """Throughput of the ID item tower (--item_tower id, the IDRec baseline) on its public path: optimizer.zero_grad(), model(ids, log_mask),
 loss.backward(), FusedAdam.step() -- one JSON line per configuration (ms/step, user-seq/s, and the inverted index's list lengths of a batch).
 
-    python tools/id_bench.py [--steps K] [--warmup W] [--only NAME]
+    python tools/id_bench.py [--steps K] [--warmup W] [--only NAME] [--loss {bce,ce}]
 
 Configurations (the reference's CV defaults: B 64, E 64, 2 blocks x 2 heads, Downstream/CV/parameters.py):
   full_L10 / full_L20     full histories at --max_seq_len 10 / 20, item_num 14 720 (the Amazon 2w catalogue), ids uniform
   real_L20                the 1 024 real user sequences of tests/golden/real_data/amazon_users_head.tsv (real lengths, real repeats), 64 per batch
   full_L20_500k           item_num 500 000: what dense Adam and zero_grad cost over a large table
+--loss ce trains with the softmax cross-entropy over the whole table (a4r_score_ce_*) and adds, per configuration, a second JSON line that times
+the head alone (forward + both backward launches on the step's own rows and table) beside the same head in eager fp32 torch.matmul +
+F.cross_entropy (forward + backward), with torch.cuda.max_memory_allocated of each above what was allocated before it ran.
 Per-kernel times: run this under `rocprofv3 --kernel-trace --stats -- python tools/id_bench.py`."""
 import argparse
 import json
@@ -22,6 +25,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 B, E = 64, 64
+FP32_MFMA_PEAK = 157.3e12   # flop/s, MI355X fp32 matrix peak: the per-launch fractions of --loss ce are relative to it
 
 
 def model_args(max_seq_len):
@@ -75,13 +79,79 @@ def make_batches(name, L, item_num, n_batches, rng):
     return [batch_from_seqs([rng.integers(1, item_num + 1, L) for _ in range(B)], L, item_num, rng) for _ in range(n_batches)]
 
 
-def run(name, max_seq_len, item_num, steps, warmup):
+def _timed(fn, steps, warmup):
+    """-> (ms per call, peak bytes allocated above the level before the first call)."""
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    base = torch.cuda.memory_allocated()
+    torch.cuda.reset_peak_memory_stats()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / steps * 1e3, torch.cuda.max_memory_allocated() - base
+
+
+def head_compare(name, model, item_num, max_seq_len, steps, warmup):
+    """The cross-entropy head alone on B x max_seq_len rows against the model's table: the three fused launches beside eager fp32
+    matmul + cross_entropy (forward and backward of both), same rows, same table, same targets."""
+    from adapter4rec_amd import _lib as L
+    R, N1 = B * max_seq_len, item_num + 1
+    g = torch.Generator().manual_seed(1)
+    table = model.id_embedding.weight.detach()
+    prec = (torch.randn(R, E, generator=g) * E ** -0.25).cuda()
+    tgt = torch.randint(1, N1, (R,), generator=g, dtype=torch.int32).cuda()
+    mask = torch.ones(R, device='cuda')
+    lse, s_tgt, lw = torch.empty(R, device='cuda'), torch.empty(R, device='cuda'), torch.empty(4, device='cuda')
+    d_prec, d_table = torch.empty(R, E, device='cuda'), torch.zeros(N1, E, device='cuda')
+    ranges = L.score_ce_ranges(R, N1)
+    ws = torch.empty(L.score_ce_ws_bytes(R, N1, E), dtype=torch.uint8, device='cuda')
+
+    def fwd():
+        L.score_ce_fwd(prec, table, tgt, mask, lse, s_tgt, lw, R, ws=ws)
+
+    def rows():
+        L.score_ce_bwd(prec, table, tgt, mask, lse, lw, 1.0, d_prec, None, R, ws=ws)
+
+    def items():
+        L.score_ce_bwd(prec, table, tgt, mask, lse, lw, 1.0, None, d_table, R)
+
+    def fused():
+        fwd()
+        L.score_ce_bwd(prec, table, tgt, mask, lse, lw, 1.0, d_prec, d_table, R, ws=ws)
+
+    pe, te, tl = prec.clone().requires_grad_(True), table.clone().requires_grad_(True), tgt.long() - 1
+
+    def eager():
+        pe.grad = te.grad = None
+        loss = torch.nn.functional.cross_entropy(torch.matmul(pe, te[1:].T), tl)
+        loss.backward()
+        return loss
+
+    fused_ms, fused_peak = _timed(fused, steps, warmup)
+    eager_ms, eager_peak = _timed(eager, steps, warmup)
+    flop = 2.0 * R * item_num * E                          # one streamed product; forward 1, bwd_rows 2, bwd_items 2
+    parts = {}
+    for nm, fn, k in (('fwd', fwd, 1), ('bwd_rows', rows, 2), ('bwd_items', items, 2)):
+        ms, _ = _timed(fn, steps, warmup)
+        parts[nm + '_ms'] = round(ms, 4)
+        parts[nm + '_mfma_fraction'] = round(k * flop / (ms * 1e-3) / FP32_MFMA_PEAK, 4)
+    return dict(config=name + '_ce_head', rows=R, item_num=item_num, embedding_dim=E, ranges=ranges, steps=steps, warmup=warmup,
+                fused_ms=round(fused_ms, 4), eager_ms=round(eager_ms, 4), fused_peak_bytes=int(fused_peak), eager_peak_bytes=int(eager_peak),
+                fused_ws_bytes=int(ws.numel()), logits_bytes=int(R * item_num * 4),
+                fused_tflops_5_products=round(5 * flop / (fused_ms * 1e-3) / 1e12, 2), **parts,
+                loss_fused=float(lw[0]), loss_eager=float(eager().detach()))
+
+
+def run(name, max_seq_len, item_num, steps, warmup, loss_kind='bce'):
     from adapter4rec_amd.cv import Model
     from adapter4rec_amd.cv.inject import optimizer_groups
     from adapter4rec_amd.optim import FusedAdam
     torch.manual_seed(0)
     rng = np.random.default_rng(0)
     args = model_args(max_seq_len)
+    args.loss = loss_kind
     args.lr, args.fine_tune_lr, args.adapter_cv_lr, args.adapter_sasrec_lr = 1e-4, 1e-4, 1e-4, 1e-4
     model = Model(args, item_num, False).to('cuda')
     model.train()
@@ -107,10 +177,11 @@ def run(name, max_seq_len, item_num, steps, warmup):
         loss = step(i)
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / steps
-    return dict(config=name, batch=B, embedding_dim=E, max_seq_len=max_seq_len, item_num=item_num, steps=steps, warmup=warmup,
+    out = dict(config=name, loss_kind=loss_kind, batch=B, embedding_dim=E, max_seq_len=max_seq_len, item_num=item_num, steps=steps, warmup=warmup,
                 ms_per_step=round(dt * 1e3, 4), user_seq_per_s=round(B / dt, 1), loss=float(loss.detach()),
                 longest_list_max=max(s['longest_list'] for s in lens), median_list_median=float(np.median([s['median_list'] for s in lens])),
                 first_batch=stats)
+    return out, model
 
 
 CONFIGS = [('full_L10', 10, 14720), ('full_L20', 20, 14720), ('real_L20', 20, 14720), ('full_L20_500k', 20, 500000)]
@@ -121,11 +192,15 @@ def main():
     ap.add_argument('--steps', type=int, default=200)
     ap.add_argument('--warmup', type=int, default=20)
     ap.add_argument('--only', default=None)
+    ap.add_argument('--loss', default='bce', choices=['bce', 'ce'])
     a = ap.parse_args()
     for name, msl, n in CONFIGS:
         if a.only and name != a.only:
             continue
-        print(json.dumps(run(name, msl, n, a.steps, a.warmup)), flush=True)
+        line, model = run(name, msl, n, a.steps, a.warmup, a.loss)
+        print(json.dumps(line), flush=True)
+        if a.loss == 'ce':
+            print(json.dumps(head_compare(name, model, n, msl, a.steps, a.warmup)), flush=True)
 
 
 if __name__ == '__main__':
