@@ -15,20 +15,16 @@ Data layout in HBM
     buffer (what RCCL all-reduces), Adam moments alongside; kernel-side bf16/transposed/padded copies
     of the adapter matrices are refreshed by one pack launch per step.
 """
-import math
 import os as _os
 
 import torch
 
 from . import _lib as L
+from .engine_blocks import _Adapter, _Block, _Dense, _KAdapter, _LN, _Lora, pad_to
 from .model.bert import backbone_geometry
-from .model.modules import AdapterBlock, AdapterPfeifferBlock, HyperComplexAdapterBlock, PHMLinear
+from .model.modules import AdapterBlock, AdapterPfeifferBlock, HyperComplexAdapterBlock
 
 FMIN = float(torch.finfo(torch.float32).min)
-
-
-def pad_to(n, m):
-    return (n + m - 1) // m * m
 
 
 def _skip_unused_items():
@@ -40,204 +36,10 @@ def _skip_unused_items():
 WGRAD_STREAM = bool(int(_os.environ.get('A4R_WGRAD_STREAM', '0')))     # 1 = adapter weight gradients on a side stream (see _adapter_wgrads): +1.3 % in round 1, neutral since the GEMM's
                                                                         # late-starting workgroups use the same idle CUs (same-box 19.07 vs 18.98 ms): off by default
 
-class _LN:
-    """LayerNorm parameters (fp32) + optional gradient sinks."""
-
-    def __init__(self, mod, eng):
-        self.gamma, self.beta, self.eps = mod.weight, mod.bias, mod.eps
-        self.g_gamma = eng.grad_view(mod.weight)
-        self.g_beta = eng.grad_view(mod.bias)
-
-
-class _Adapter:
-    """One bottleneck adapter: kernel-side copies (compute dtype, bottleneck padded to 64) + gradient sinks."""
-
-    def __init__(self, mod, width, eng, dt):
-        self.kind = mod.kind
-        self.act = L.ACT_BY_NAME[mod.activation_name]
-        dev = eng.dev
-        if isinstance(mod, HyperComplexAdapterBlock):
-            self.d = mod.down_sampler.out_features
-            self.virtual = (mod.down_sampler, mod.up_sampler)
-            b_down, b_up = mod.down_sampler.b, mod.up_sampler.b
-            for lin in self.virtual:     # gradients of these arrive through _virtual_backward
-                for q in (lin.W_left, lin.W_right, lin.phm_rule):
-                    if q is not None:
-                        eng.grad_view(q)
-        else:
-            self.d = mod.fc_down.out_features
-            self.virtual = None
-            self.p_wd, self.p_wu = mod.fc_down.weight, mod.fc_up.weight
-            b_down, b_up = mod.fc_down.bias, mod.fc_up.bias
-        self.dp = pad_to(self.d, 64)
-        self.width = width
-        self.wd = torch.zeros(self.dp, width, dtype=dt, device=dev)      # fc_down.weight  [d, H]
-        self.wdT = torch.zeros(width, self.dp, dtype=dt, device=dev)
-        self.wu = torch.zeros(width, self.dp, dtype=dt, device=dev)      # fc_up.weight    [H, d]
-        self.wuT = torch.zeros(self.dp, width, dtype=dt, device=dev)
-        self.p_bd, self.p_bu = b_down, b_up
-        self.bd = torch.zeros(self.dp, dtype=torch.float32, device=dev)  # padded copy of fc_down.bias
-        self.bu = b_up                                                   # [H] fp32, used in place
-        self.g_bu = eng.grad_view(b_up)
-        self.g_bd = eng.grad_view(b_down)
-        self.g_wd = self.g_wu = None
-        # the same four matrices in the FRAGMENT order of the one-launch adapter kernels (a4r_pack_matrices layouts 1 / 2, include/a4r.h: every wave
-        # instruction of those kernels' prologues then reads 1 KiB contiguous; the first tile of a launch starts ~3 us earlier).  Row-major copies stay:
-        # the three-launch forms, the weight-gradient kernels' shapes and the tests read them.  (fwd: wd, wu; bwd: wuT, wdT)
-        self.frag_f = self.frag_b = None
-        if dt == torch.bfloat16 and self.dp == 64 and width in (128, 256, 512, 768, 1024):
-            mk = lambda: torch.zeros(64 * width, dtype=dt, device=dev)
-            self.frag_f, self.frag_b = (mk(), mk()), (mk(), mk())
-        if self.virtual is None:
-            self.g_wd, self.g_wu = eng.grad_view(self.p_wd), eng.grad_view(self.p_wu)
-            eng.add_pack(self.p_wd, self.wd, False)
-            eng.add_pack(self.p_wd, self.wdT, True)
-            eng.add_pack(self.p_wu, self.wu, False)
-            eng.add_pack(self.p_wu, self.wuT, True)
-            if self.frag_f is not None:
-                for p_, dst, code in self.frag_entries():
-                    eng.add_pack(p_, dst, code)
-        else:
-            eng.add_virtual(self)
-        eng.add_pack_bias(b_down, self.bd)
-        # scratch for padded weight gradients (used when d < dp, or for virtual matrices)
-        direct = self.virtual is None and self.d == self.dp
-        self.s_wd = None if direct else eng.scratch(self.dp, width)
-        self.s_wu = None if direct else eng.scratch(width, self.dp)
-        self.s_bd = None if self.d == self.dp else eng.scratch(1, self.dp)[0]
-        if self.virtual is None and not direct:          # the valid corners go into the flat gradient at the end of backward
-            eng.add_corner(self.s_wu, self.p_wu, width, self.d)
-            eng.add_corner(self.s_wd, self.p_wd, self.d, width)
-        if self.s_bd is not None:
-            eng.add_corner(self.s_bd.view(1, -1), b_down, 1, self.d)
-
-    def frag_entries(self, wd_src=None, wu_src=None):
-        """(source, destination, a4r_pack_desc_t.transpose code) of the four fragment-ordered copies: bit 0 transpose, bits 1-2 layout (1: [64, H], 2: [H, 64]);
-        destinations are viewed with their LOGICAL shape so that the descriptor carries rows_pad / cols_pad"""
-        wd_src = self.p_wd if wd_src is None else wd_src
-        wu_src = self.p_wu if wu_src is None else wu_src
-        W = self.width
-        return [(wd_src, self.frag_f[0].view(64, W), 2), (wu_src, self.frag_f[1].view(W, 64), 4),
-                (wu_src, self.frag_b[0].view(64, W), 2 | 1), (wd_src, self.frag_b[1].view(W, 64), 4 | 1)]
-
-
-class _Lora:
-    """LoRA on one projection (q or v) of a fused qkv weight: W_eff = W + B A / r is re-merged into the packed qkv operand
-    every step (so forward and dgrad cost nothing extra); the low-rank gradients come from four skinny products in backward:
-    t = x A^T, dt = (dq B) s, dB = dq^T t s, dA = dt^T x."""
-
-    ONES_COL = 32            # (shared form: rank columns 0 - 7 and 16 - 23 are in use)
-
-    def __init__(self, mod, width, eng, dt, slot, share=None):
-        """share = (dict, off): this LoRA is one of a block's two small-rank ones (r <= 16: the image tower's q, v at r = 8).  They then use
-        ONE [64, width] A operand (rank rows at off .. off + r), ONE t = x A^T and ONE dA = dt^T x launch; only the products that read
-        this projection's own gradient (dt = dq B, dB = dq^T t, the bias sum) stay per LoRA.  The rank was padded to 64 columns anyway."""
-        self.mod, self.slot, self.width = mod, slot, width
-        self.r, self.rp, self.scaling = mod.r, pad_to(mod.r, 64), float(mod.scaling)
-        dev = eng.dev
-        self.g_bias = eng.grad_view(mod.bias) if mod.bias is not None else None
-        self.g_W = None
-        self.share = None
-        if self.r == 0:                  # loralib: r = 0 leaves a plain Linear whose weight stays trainable (CV run_adapter.py:394)
-            self.g_W = eng.grad_view(mod.weight)
-            return
-        self.g_A, self.g_B = eng.grad_view(mod.lora_A), eng.grad_view(mod.lora_B)
-        self.BT = torch.zeros(self.rp, width, dtype=dt, device=dev)       # lora_B^T [r, out]     (NT operand of dt = dq B)
-        self.s_B = eng.scratch(width, self.rp)
-        if share is not None:
-            sh, off = share
-            self.share, self.off = sh, off
-            if 'A' not in sh:
-                sh['A'] = torch.zeros(self.rp, width, dtype=dt, device=dev)
-                sh['s_A'] = eng.scratch(self.rp, width)
-            self.A, self.s_A = sh['A'], sh['s_A']
-            eng.add_pack(mod.lora_A, sh['A'][off:off + 16], False)                   # rows off .. off + r (zero-padded to 16)
-            eng.add_pack(mod.lora_B, self.BT[off:off + 16], True)                    # B^T at the same rank rows: dt lands in columns off .. off + r
-            eng.add_corner(self.s_B[:, off:off + 16], mod.lora_B, width, self.r, alpha=self.scaling)
-            eng.add_corner(sh['s_A'][off:off + 16], mod.lora_A, self.r, width)
-            # the bias gradient (column sums of this projection's gradient) rides in the dB product: column ONES_COL of t is a column of
-            # ones (a bias of the t = x A^T launch: row ONES_COL of A is zero), so (dq^T t)[:, ONES_COL] = sum over rows of dq
-            if 'ones' not in sh:
-                sh['ones'] = torch.zeros(self.rp, dtype=torch.float32, device=dev)
-                sh['ones'][self.ONES_COL] = 1.0
-            if self.g_bias is not None:
-                eng.add_corner(self.s_B[:, self.ONES_COL:self.ONES_COL + 1], mod.bias, width, 1)
-            return
-        self.A = torch.zeros(self.rp, width, dtype=dt, device=dev)        # lora_A [r, in]        (NT operand of t = x A^T)
-        eng.add_pack(mod.lora_A, self.A, False)
-        eng.add_pack(mod.lora_B, self.BT, True)
-        self.s_A = eng.scratch(self.rp, width)
-        eng.add_corner(self.s_B, mod.lora_B, width, self.r, alpha=self.scaling)      # dB = (dq^T t) s
-        eng.add_corner(self.s_A, mod.lora_A, self.r, width)
-
-    @classmethod
-    def for_block(cls, lins, width, eng, dt):
-        """The _Lora objects of a block's (query, key, value) projections; two small-rank ones share their A-side launches."""
-        idx = [i for i, lin in enumerate(lins) if type(lin).__name__ == 'LoRALinear']
-        small = [i for i in idx if 0 < lins[i].r <= 16]
-        share = {} if (len(small) == 2 and len(idx) == 2) else None
-        out = []
-        for i in idx:
-            out.append(cls(lins[i], width, eng, dt, i, share=(share, 16 * small.index(i)) if share is not None else None))
-        return out
-
-
-class _Block:
-    """One post-LN transformer block (BERT layer or SASRec block) with optional adapters."""
-    train_dense = False          # any backbone Linear of the block trainable (--fine_tune_to all)
-    qkv = (None, None, None)
-    d_o = d_i = d_o2 = None
-
-
-class _Dense:
-    """One Linear of the backbone: compute-dtype copies W [out, in] (NT operand) and W^T (dgrad operand).  Frozen: filled once.
-    Trainable (--fine_tune_to all, Pretraining/): the copies are re-packed from the flat fp32 master every step and g_w / g_b
-    receive dW = dY^T X (a4r_gemm_tn) and db = column sums of dY (a4r_colsum)."""
-
-    def __init__(self, eng, weight, bias, dt, w_dst=None, wT_dst=None, b_dst=None, view2d=None, pad=None):
-        out_f, in_f = view2d if view2d is not None else weight.shape          # view2d: a Conv2d weight seen as [out, C*kh*kw]
-        op, ip = pad if pad is not None else (out_f, in_f)                     # pad: zero-padded storage (K-Adapter blocks 16 -> 64 wide)
-        self.view2d, self.out_f, self.in_f = view2d, out_f, in_f
-        self.w = w_dst if w_dst is not None else torch.zeros(op, ip, dtype=dt, device=eng.dev)
-        self.wT = wT_dst if wT_dst is not None else torch.zeros(ip, op, dtype=dt, device=eng.dev)
-        padded = tuple(self.w.shape) != (out_f, in_f)
-        if weight.requires_grad:
-            eng.add_pack(weight, self.w, False)
-            eng.add_pack(weight, self.wT, True)
-        else:
-            w2 = weight.detach().reshape(out_f, in_f)
-            self.w[:out_f, :in_f].copy_(w2.to(dt))
-            self.wT[:in_f, :out_f].copy_(w2.t().to(dt))
-        self.g_w = eng.grad_view(weight)
-        self.s_w = eng.scratch(*self.w.shape) if (padded and self.g_w is not None) else None
-        if self.s_w is not None:
-            eng.add_corner(self.s_w, weight, out_f, in_f)
-        self.b = self.g_b = self.s_b = None
-        if bias is not None:
-            if b_dst is None and padded:
-                b_dst = torch.zeros(self.w.shape[0], dtype=torch.float32, device=eng.dev)
-            if b_dst is not None:
-                self.b = b_dst
-                if bias.requires_grad:
-                    eng.add_pack_bias(bias, b_dst[:out_f])
-                else:
-                    b_dst[:out_f].copy_(bias.detach().float())
-            else:
-                self.b = bias.data if bias.requires_grad else eng._f32(bias)     # trainable: the fp32 master (a flat_p view) itself
-            self.g_b = eng.grad_view(bias)
-            if padded and self.g_b is not None:
-                self.s_b = eng.scratch(1, self.w.shape[0])[0]
-                eng.add_corner(self.s_b.view(1, -1), bias, 1, out_f)
-        self.trainable = self.g_w is not None or self.g_b is not None
-
-
-class _KAdapter:
-    """Engine side of one KAdapterBlock (modules.py:161-206): down (trainable Linear) -> two plain post-LN blocks (all weights
-    trainable, no mask, not causal) -> up, + input."""
-    pass
-
 
 class TransRecEngine:
+    MULTI_ATTR = True           # --news_attributes: several text attributes per item through the same tower (the image and ID towers have one input per item)
+
     def __init__(self, model, args, arch='sasrec', dtype='bf16', phm_owner=None):
         self.model, self.args, self.arch = model, args, arch
         self.root = phm_owner if phm_owner is not None else model
@@ -270,7 +72,7 @@ class TransRecEngine:
             if nw:
                 self.attrs.append((st, nw))
             st += 2 * nw
-        self.n_attr = len(self.attrs) if type(self).__name__ == 'TransRecEngine' else 1
+        self.n_attr = len(self.attrs) if self.MULTI_ATTR else 1
         self.S = max(nw for _, nw in self.attrs) if self.attrs else getattr(args, 'num_words_title', 0)      # (a single attribute: its own length)
         self.S0 = self.S                           # the title length of the data; self.S may be shorter for one training step (train_forward)
         self.E = args.embedding_dim
@@ -279,6 +81,14 @@ class TransRecEngine:
         self.step_count = 0
         self._packs_T, self._packs_b, self._virtual = [], [], []
         self._arena, self._arena_used, self._corners, self._corner_tab = [], 0, [], None
+        # caches and per-step state that are filled at first use: None / 0 / empty = not there yet
+        self._lora_tabs = None                     # a4r_lora_merge_batch tables (pack_trainables)
+        self._layer_descs, self._attr_tabs = {}, {}
+        self._kad_saved_b, self._kad_saved_s, self._kad_saved_M, self._kad_saved_Mu = None, None, 0, 0
+        self._saved_Ip = None
+        self._chunks = 0                           # _grad_chunks' plan; 0 = not derived yet (None is a plan: the single all-reduce)
+        self._exch = None                          # (ddp, chunks, done, final) during an overlapped data-parallel backward
+        self.next_noise = None                     # ViT-MAE: explicit masking noise of the next step (parity runs)
         self._collect_trainables()
         for p in self.trainable_params:            # resumed run (FusedAdam.load_state_dict): the counter-based dropout stream continues
             if getattr(p, '_a4r_resume_step', None) is not None:
@@ -329,8 +139,6 @@ class TransRecEngine:
         # block input and the attention-output sub-layer's LayerNorm output leave the fused adapter kernel as e4m3 + row scale)
         ok = lambda w: w.shape[0] % 256 == 0 and w.shape[1] % 128 == 0
         for b in self.bert_blocks:
-            b.wqkv8 = b.wi8 = b.wo8 = b.wo28 = b.wo2T8 = b.wiT8 = None
-            b.wqkv8_dyn = False
             frozen_qkv = not b.lora and all(d is not None and not d.trainable for d in b.qkv)
             if frozen_qkv and ok(b.wqkv):
                 b.wqkv8, b.wqkv8s = L.quantize_weight_fp8(b.wqkv)
@@ -549,7 +357,7 @@ class TransRecEngine:
         for tab, n, mx, c in self._tabs:
             L.pack_matrices(self.flat_p, tab, n, mx, c)
         # LoRA: re-merge W + B A / r into the packed qkv operands -- every LoRA-carrying projection of a dtype in one launch (a4r_lora_merge_batch)
-        if getattr(self, '_lora_tabs', None) is None:
+        if self._lora_tabs is None:
             groups = {}
             for blk in self.bert_blocks + self.sas_blocks:
                 for lo in blk.lora:
@@ -562,7 +370,7 @@ class TransRecEngine:
             L.lora_merge_batch(tab)
         if self.fp8:
             for blk in self.bert_blocks:
-                if getattr(blk, 'wqkv8_dyn', False):
+                if blk.wqkv8_dyn:
                     L.quant_rows_fp8(blk.wqkv, blk.wqkv8, blk.wqkv8s.view(-1, 1))
         if self._virtual:
             if self._phm_tab is not None:                     # Compacter: effective matrices from (phm_rule, W_left, W_right), one launch
@@ -605,8 +413,12 @@ class TransRecEngine:
         if self.geo['hidden_act'] not in ('gelu',):
             raise NotImplementedError(f"hidden_act {self.geo['hidden_act']}")
         self._build_bert(bert)
-        self._build_head()
+        self._build_head(self.model.bert_encoder.text_encoders['title'].fc)
         self.bert_trains = any(p.requires_grad for p in bert.parameters())
+        self._build_item_kads(kmod)
+
+    def _build_item_kads(self, kmod):
+        """The K-Adapters over the item tower's hidden states (kmod: the wrapper that holds them, or None)."""
         self.bert_kads, self.bert_klist, self.d_com = [], [], None
         if kmod is not None:
             nb = len(self.bert_blocks)
@@ -658,46 +470,23 @@ class TransRecEngine:
         self.p_attn = float(g['attention_probs_dropout_prob'])
         self.bert_blocks = []
         for i, layer in enumerate(bert.encoder.layer):
-            b = _Block()
             att = layer.attention.self
-            for lin in (att.query, att.key, att.value):
-                if type(lin).__name__ not in ('LoRALinear', 'Linear'):
-                    raise NotImplementedError(f'projection module {type(lin).__name__}')
-            b.lora = _Lora.for_block((att.query, att.key, att.value), H, self, self.T)
-            b.H, b.F, b.nh, b.dh, b.S = H, self.F, nh, H // nh, self.S
+            b = _Block(self, (att.query, att.key, att.value), H, H, self.F, nh, self.S, self.T, True, L.ACT_GELU)
             b.is_item = True                       # (a block of the item tower: follows self._pk)
             b.long = self.S > 32                   # titles of more than 32 tokens: a4r_attn_long_* with the key mask (any step length <= S)
-            b.causal, b.mask_neg, b.scale = False, FMIN, 1.0 / math.sqrt(H // nh)
-            b.ffn_act = L.ACT_GELU
+            b.mask_neg = FMIN
             b.p_hidden, b.p_attn, b.site = self.p_hidden, self.p_attn, 16 * i
-            b.wqkv = torch.zeros(3 * H, H, dtype=self.T, device=self.dev)
-            b.wqkvT = torch.zeros(H, 3 * H, dtype=self.T, device=self.dev)
-            b.bqkv = torch.zeros(3 * H, dtype=torch.float32, device=self.dev)
-            self._pack_lora_bias(b, H)
-            b.qkv = tuple(None if type(lin).__name__ == 'LoRALinear' else          # LoRA slots are merged in pack_trainables
-                          _Dense(self, lin.weight, lin.bias, self.T, b.wqkv[sl * H:(sl + 1) * H], b.wqkvT[:, sl * H:(sl + 1) * H],
-                                 b.bqkv[sl * H:(sl + 1) * H])
-                          for sl, lin in enumerate((att.query, att.key, att.value)))
-            d1, ln1, ad1, pl1, lnn1 = self._so(layer.attention.output, H, self.T)
-            d2, ln2, ad2, pl2, lnn2 = self._so(layer.output, H, self.T)
-            b.d_o = _Dense(self, d1.weight, d1.bias, self.T)
-            b.d_i = _Dense(self, layer.intermediate.dense.weight, layer.intermediate.dense.bias, self.T)
-            b.d_o2 = _Dense(self, d2.weight, d2.bias, self.T)
-            b.wo, b.woT, b.bo = b.d_o.w, b.d_o.wT, b.d_o.b
-            b.wi, b.wiT, b.bi = b.d_i.w, b.d_i.wT, b.d_i.b
-            b.wo2, b.wo2T, b.bo2 = b.d_o2.w, b.d_o2.wT, b.d_o2.b
-            b.train_dense = any(d is not None and d.trainable for d in b.qkv + (b.d_o, b.d_i, b.d_o2))
+            d1, ln1, b.ad1, b.pl1, b.lnn1 = self._so(layer.attention.output, H, self.T)
+            d2, ln2, b.ad2, b.pl2, b.lnn2 = self._so(layer.output, H, self.T)
+            b.set_dense(self, d1, layer.intermediate.dense, d2)
             b.ln1, b.ln2 = _LN(ln1, self), _LN(ln2, self)
-            b.ad1, b.ad2, b.pl1, b.pl2, b.lnn1, b.lnn2 = ad1, ad2, pl1, pl2, lnn1, lnn2
             b.need_dx = i > 0 or self.train_emb
-            b.T = self.T
             self.bert_blocks.append(b)
         lastb = self.bert_blocks[-1]
         if lastb.pl1 == 'parallel' or lastb.pl2 == 'parallel':
             self.cls_only = False                  # the parallel form needs the sub-layer inputs per token row
 
-    def _build_head(self):
-        fc = self.model.bert_encoder.text_encoders['title'].fc
+    def _build_head(self, fc):
         self.d_fc = _Dense(self, fc.weight, fc.bias, self.T)
         self.fc_w, self.fc_b = self.d_fc.w, self.d_fc.b        # [E, H] compute dtype (forward operand)
         self.fc_wT32 = torch.zeros(fc.in_features, fc.out_features, dtype=torch.float32, device=self.dev)   # [H, E] fp32 (dgrad operand: d_pre is fp32)
@@ -725,16 +514,16 @@ class TransRecEngine:
         self.sas_blocks = []
         kad = type(te.transformer_blocks).__name__ == 'SASRecKAdaptedTransformerBlocks'       # model.py:562-583
         block_list = te.transformer_blocks.transformer_blocks if kad else te.transformer_blocks
-        for j, blk in enumerate(block_list):
-            tb = blk.transformer_block if hasattr(blk, 'transformer_block') else blk
+        for j, mod in enumerate(block_list):
+            tb = mod.transformer_block if hasattr(mod, 'transformer_block') else mod
             b = self._make_block(tb, E, nh, self.Lseq - 1, f32, True, -1e9, self.p_sas, 4096 + 16 * j)
-            placement = getattr(blk, 'placement', None) if blk is not tb else None
-            if blk is not tb:
+            placement = getattr(mod, 'placement', None) if mod is not tb else None
+            if mod is not tb:
                 if placement == 'pfeiffer':
-                    b.ad2, b.pl2, b.lnn2 = self._adapter_of(blk, 'adapter', E, f32), 'pfeiffer', _LN(blk.LN, self)
+                    b.ad2, b.pl2, b.lnn2 = self._adapter_of(mod, 'adapter', E, f32), 'pfeiffer', _LN(mod.LN, self)
                 else:
-                    b.ad1 = self._adapter_of(blk, 'adapter1', E, f32)
-                    b.ad2 = self._adapter_of(blk, 'adapter2', E, f32)
+                    b.ad1 = self._adapter_of(mod, 'adapter1', E, f32)
+                    b.ad2 = self._adapter_of(mod, 'adapter2', E, f32)
                     b.pl1 = (placement or 'serial') if b.ad1 else None
                     b.pl2 = (placement or 'serial') if b.ad2 else None
             self.sas_blocks.append(b)
@@ -751,7 +540,7 @@ class TransRecEngine:
         if self.sas_kads or not self.sas_blocks or self.Lseq - 1 > 32:
             return False
         for b in self.sas_blocks:
-            if (b.H, getattr(b, 'Hv', b.H), b.nh, b.F, b.T) != (64, 64, 2, 256, torch.float32) or not b.causal or b.lora or b.train_dense:
+            if (b.H, b.Hv, b.nh, b.F, b.T) != (64, 64, 2, 256, torch.float32) or not b.causal or b.lora or b.train_dense:
                 return False
             pfe = b.ad1 is None and b.ad2 is not None and b.pl2 == 'pfeiffer' and b.lnn2 is not None       # SASRecPfeifferAdaptedSelfOutput
             ser = b.ad1 is not None and b.ad2 is not None and b.pl1 == 'serial' and b.pl2 == 'serial' and b.lnn1 is None and b.lnn2 is None
@@ -792,52 +581,19 @@ class TransRecEngine:
         LayerNorms run on the valid columns only (b.Hv)."""
         mha, ff = tb.multi_head_attention, tb.feed_forward
         H = pad_to(Hv, 64)
-        Fv = ff.w_1.out_features
-        F = pad_to(Fv, 64)
+        F = pad_to(ff.w_1.out_features, 64)
         dh = Hv // nh
         long = S > 32                 # K-Adapter blocks over the ViT token rows (S = 197 / 50): a4r_attn_long_*, no mask, dh 64 / 32
         wide = dh in (128, 256) and dt == torch.float32 and not long          # (the user tower at --embedding_dim 256 / 512)
         wide_long = long and dh == 128 and dt == torch.float32 and S <= 128      # (--embedding_dim 256 with two heads AND --max_seq_len 33 .. 128: the long kernels' fp32 head width 128)
         if dh not in (32, 64) and not wide and not wide_long and not (0 < dh <= 16 and not long) or S > 256 or (long and H != Hv):
             raise NotImplementedError(f'transformer block geometry width={Hv} heads={nh} S={S}')
-        b = _Block()
-        b.long = long
-        for lin in (mha.w_Q, mha.w_K, mha.w_V):
-            if type(lin).__name__ not in ('LoRALinear', 'Linear'):
-                raise NotImplementedError(f'projection module {type(lin).__name__}')
-        b.lora = _Lora.for_block((mha.w_Q, mha.w_K, mha.w_V), Hv, self, dt)
-        if b.lora and H != Hv:
-            raise NotImplementedError('LoRA on a zero-padded block')
-        b.H, b.Hv, b.F, b.nh, b.dh, b.S = H, Hv, F, nh, dh, S
-        b.causal, b.mask_neg, b.scale = causal, mask_neg, 1.0 / math.sqrt(dh)
-        b.ffn_act = L.ACT_RELU
+        b = _Block(self, (mha.w_Q, mha.w_K, mha.w_V), H, Hv, F, nh, S, dt, False, L.ACT_RELU)
+        b.long, b.causal, b.mask_neg = long, causal, mask_neg
         b.p_hidden, b.p_attn, b.site = p_drop, p_drop, site
-        b.wqkv = torch.zeros(3 * H, H, dtype=dt, device=self.dev)
-        b.wqkvT = torch.zeros(H, 3 * H, dtype=dt, device=self.dev)
-        b.bqkv = torch.zeros(3 * H, dtype=torch.float32, device=self.dev) if b.lora else None       # lora.Linear carries a bias
-        self._pack_lora_bias(b, H)
-        b.qkv = tuple(None if type(lin).__name__ == 'LoRALinear' else
-                      _Dense(self, lin.weight, None, dt, b.wqkv[sl * H:(sl + 1) * H], b.wqkvT[:, sl * H:(sl + 1) * H])
-                      for sl, lin in enumerate((mha.w_Q, mha.w_K, mha.w_V)))
-        b.d_o = _Dense(self, mha.fc.weight, None, dt, pad=(H, H))
-        b.d_i = _Dense(self, ff.w_1.weight, ff.w_1.bias, dt, pad=(F, H))
-        b.d_o2 = _Dense(self, ff.w_2.weight, ff.w_2.bias, dt, pad=(H, F))
-        b.wo, b.woT, b.bo = b.d_o.w, b.d_o.wT, None
-        b.wi, b.wiT, b.bi = b.d_i.w, b.d_i.wT, b.d_i.b
-        b.wo2, b.wo2T, b.bo2 = b.d_o2.w, b.d_o2.wT, b.d_o2.b
-        b.train_dense = any(d is not None and d.trainable for d in b.qkv + (b.d_o, b.d_i, b.d_o2))
+        b.set_dense(self, mha.fc, ff.w_1, ff.w_2)
         b.ln1, b.ln2 = _LN(mha.layer_norm, self), _LN(ff.layer_norm, self)
-        b.ad1 = b.ad2 = b.lnn1 = b.lnn2 = None
-        b.pl1 = b.pl2 = None
-        b.need_dx = True
-        b.T = dt
         return b
-
-    def _pack_lora_bias(self, b, H):
-        """lora.Linear keeps a (trainable) bias: its fp32 master is copied into the fused qkv bias by the per-step pack launch."""
-        for lo in b.lora:
-            if lo.mod.bias is not None:
-                self.add_pack_bias(lo.mod.bias, b.bqkv[lo.slot * H:(lo.slot + 1) * H])
 
     def _make_kadapter(self, mod, width, S, dt, site):
         k = _KAdapter()
@@ -910,26 +666,25 @@ class TransRecEngine:
         """This block's saved FFN activation derivative is the uint8 form (GELU FFN, bf16 storage)."""
         if blk.d_i is not None and (blk.d_i.trainable or blk.d_o2.trainable):
             return False             # --fine_tune_to all: dW_i / dx1 of a TRAINABLE FFN use the derivative at storage precision, not the 8-bit form
-        return self.q8_deriv and blk.T == torch.bfloat16 and getattr(blk, 'ffn_act', L.ACT_GELU) == L.ACT_GELU and blk.F % 16 == 0
+        return self.q8_deriv and blk.T == torch.bfloat16 and blk.ffn_act == L.ACT_GELU and blk.F % 16 == 0
 
     def _vskip(self, blk, which):
         """Sub-layer `which` of a post-LN block keeps y = LN(v) per layer (the tensor the next GEMM reads anyway) instead of v, and the fused
         adapter backward rebuilds xhat = (y - beta) / gamma: 62 MB less written per fused forward launch at B = 32.  Needs the one-launch
         kernels (bf16, serial Houlsby / Compacter placement), a frozen LayerNorm and |gamma| bounded away from 0."""
         ad, pl, ln = (blk.ad1, blk.pl1, blk.ln1) if which == '1' else (blk.ad2, blk.pl2, blk.ln2)
-        if ad is None or pl != 'serial' or hasattr(blk, 'lnA') or blk.T != torch.bfloat16:
+        if ad is None or pl != 'serial' or blk.lnA is not None or blk.T != torch.bfloat16:
             return False
-        if not (getattr(blk, 'Hv', blk.H) == blk.H and blk.H in (128, 256, 512, 768) and ad.dp == 64):
+        if not (blk.Hv == blk.H and blk.H in (128, 256, 512, 768) and ad.dp == 64):
             return False
         if ln.g_gamma is not None or ln.g_beta is not None:
             return False
-        key = '_vskip_ok' + which
-        if not hasattr(blk, key):
+        if blk.vskip_ok[which] is None:
             # xhat = (y - beta) / gamma from the bf16-rounded y carries an error of ~2^-9 |xhat + beta / gamma|: a column with a small
             # gamma next to a sizeable beta would put O(0.1 - 1) into xhat (ADVICE r3) -- such layers keep v
             g, b = ln.gamma.detach().float(), ln.beta.detach().float()
-            setattr(blk, key, bool(float(g.abs().min()) > 1e-3 and float((b / g).abs().max()) < 8.0))
-        return getattr(blk, key)
+            blk.vskip_ok[which] = bool(float(g.abs().min()) > 1e-3 and float((b / g).abs().max()) < 8.0)
+        return blk.vskip_ok[which]
 
     def _q8t(self, blk, M):
         """The 8-bit derivative tensor in the 256-tile kernel's own order (a4r_gemm_t.q8_tiled): only its writer (FFN-up) and its reader
@@ -943,7 +698,7 @@ class TransRecEngine:
         T, H, F = blk.T, blk.H, blk.F
         d = {}
         d['qkv'] = self._buf(pre + '.qkv', M, 3 * H, T)
-        if getattr(blk, 'long', False):              # a4r_attn_long_*: row log-sum-exp, and the forward output for delta = dO . O
+        if blk.long:              # a4r_attn_long_*: row log-sum-exp, and the forward output for delta = dO . O
             d['lse'] = self._buf(pre + '.lse', (M // blk.S + 1) * blk.nh * blk.S, 1, torch.float32)
             if not shared:
                 d['ctx_o'] = self._buf(pre + '.ctx_o', M, H, T)
@@ -977,8 +732,7 @@ class TransRecEngine:
     @staticmethod
     def _vc(blk, t):
         """The valid columns of a zero-padded block's activation (LayerNorm width), the tensor itself otherwise."""
-        hv = getattr(blk, 'Hv', blk.H)
-        return t if hv == t.shape[1] else t[:, :hv]
+        return t if blk.Hv == t.shape[1] else t[:, :blk.Hv]
 
     # ------------------------------------------------------------------ one block, forward
     def _sub_forward(self, blk, which, dense_in, w, bias, resid, ln, ad, pl, lnn, bufs, M, p_drop, site, seed, out, scales=None, out8=None):
@@ -999,7 +753,7 @@ class TransRecEngine:
         # soft prompt; Pfeiffer's FFN half): the dense output leaves the GEMM alone (bf16, as the reference's autocast Linear does), the
         # residual -- the fp32 twin the sub-layer below left, or the bf16 tensor itself at the first layer -- is added in fp32 inside
         # a4r_ln_fwd_sum, which normalises the unrounded sum and leaves the fp32 twin of its own output.
-        r32mode = self.res32 and blk.T == torch.bfloat16 and getattr(blk, 'Hv', blk.H) == blk.H and v is not None and v.shape[1] == blk.H
+        r32mode = self.res32 and blk.T == torch.bfloat16 and blk.Hv == blk.H and v is not None and v.shape[1] == blk.H
         if ad is None:
             if r32mode:
                 hd = self._buf('res32.h', M, blk.H, blk.T)
@@ -1066,18 +820,18 @@ class TransRecEngine:
     _pk = None
 
     def _off(self, blk):
-        return self._pk['off'] if (self._pk is not None and getattr(blk, 'is_item', False)) else None
+        return self._pk['off'] if (self._pk is not None and blk.is_item) else None
 
     def _cls_gather(self, src, dst, n_items, S, blk=None):
         """dst[i] = row of token 0 of item i"""
-        if self._pk is not None and (blk is None or getattr(blk, 'is_item', False)):
+        if self._pk is not None and (blk is None or blk.is_item):
             L.rows_idx_copy(src, dst, self._pk['off'], n_items)
         else:
             L.gather_rows(src, dst, n_items, S)
 
     def _cls_scatter_fill(self, src, dst, n_items, S, M, blk=None):
         """dst[row of token 0 of item i] = src[i], every other row < M zero"""
-        if self._pk is not None and (blk is None or getattr(blk, 'is_item', False)):
+        if self._pk is not None and (blk is None or blk.is_item):
             L.zero(dst[:M])
             L.rows_idx_copy(src, dst, self._pk['off'], n_items, scatter=True)
         else:
@@ -1094,7 +848,7 @@ class TransRecEngine:
 
     def _fuse(self, blk, ad, t):
         """The one-launch adapter kernels apply (bf16, bottleneck 64, a width they are instantiated for, no zero-padded block)."""
-        return getattr(blk, 'Hv', blk.H) == blk.H and L.adapter_ln_ok(t, ad.dp)
+        return blk.Hv == blk.H and L.adapter_ln_ok(t, ad.dp)
 
     # ---- one C call per layer (a4r_encoder_layer_fwd / _bwd, ABI 409): the launches below, sequenced by the library for the layers it covers --
     # bf16, short attention, serial Houlsby adapters on the one-launch kernels on both halves, frozen backbone.  Bit-identical to the per-launch path
@@ -1107,7 +861,7 @@ class TransRecEngine:
             return False
         if (self._LAYER_DBG == '2' and backward) or (self._LAYER_DBG == '3' and not backward):
             return False
-        if cls_rows is not None or getattr(blk, 'long', False) or blk.lora or blk.train_dense or hasattr(blk, 'lnA') or getattr(blk, 'Hv', blk.H) != blk.H:
+        if cls_rows is not None or blk.long or blk.lora or blk.train_dense or blk.lnA is not None or blk.Hv != blk.H:
             return False
         if any(k in bufs for k in ('xin', 'x1s', 'ctx_s', 'u_s')) or blk.ffn_act != L.ACT_GELU or blk.S > 32 or blk.H not in (128, 256, 512, 768):
             return False
@@ -1125,7 +879,7 @@ class TransRecEngine:
     def _layer_desc(self, blk, bufs, M):
         """The a4r_encoder_layer_t of (block, buffer set): static fields once, the per-step ones (seed, item count, masks, twins) by the caller."""
         key = (id(blk), id(bufs), M)
-        cache = self.__dict__.setdefault('_layer_descs', {})
+        cache = self._layer_descs
         hit = cache.get(key)
         if hit is not None and hit['bufs'] is bufs:        # (the entry keeps the buffer set alive: its id cannot be re-used by another one)
             return hit
@@ -1213,7 +967,7 @@ class TransRecEngine:
             return None
         pa = blk.p_attn if train else 0.0
         ph = blk.p_hidden if train else 0.0
-        f8 = self.fp8 and T == torch.bfloat16 and M % 256 == 0 and getattr(blk, 'wqkv8', None) is not None
+        f8 = self.fp8 and T == torch.bfloat16 and M % 256 == 0 and blk.wqkv8 is not None
         if f8:
             if x8 is None:
                 x8 = (self._buf('x8', M, H, torch.uint8), self._buf('x8s', M, 1, torch.float32))
@@ -1223,7 +977,7 @@ class TransRecEngine:
             L.gemm_nt(x, blk.wqkv, bufs['qkv'], bias=blk.bqkv, M=M)
         if 'xin' in bufs and x.data_ptr() != bufs['xin'].data_ptr():
             L.gather_rows(x, bufs['xin'], M, 1)      # LoRA backward needs the block input (t = x A^T, dA = dt^T x)
-        if getattr(blk, 'long', False):
+        if blk.long:
             ctx = bufs['ctx_o'] if 'ctx_o' in bufs else self._buf('ctx', M, H, T)
             L.attn_long_fwd(bufs['qkv'], ctx, bufs['lse'], n_items, blk.S, blk.nh, blk.dh, 0, H, 2 * H, blk.scale,
                             drop_p=pa, drop_site=blk.site, drop_seed=seed, key_mask=key_mask, causal=blk.causal)
@@ -1255,9 +1009,9 @@ class TransRecEngine:
                 raise RuntimeError('y1 and x1s are the same tensor: one of them should not have been allocated')
             x1 = bufs['y1']
         f8 = self.fp8 and T == torch.bfloat16 and M % 256 == 0             # (M: the CLS rows in the last layer)
-        f8_o = f8 and getattr(blk, 'wo8', None) is not None and 'ctx_s' not in bufs
-        f8_up = f8 and getattr(blk, 'wi8', None) is not None and blk.ffn_act == L.ACT_GELU
-        f8_ffn = f8_up and getattr(blk, 'wo28', None) is not None and 'u_s' not in bufs and self._q8(blk)
+        f8_o = f8 and blk.wo8 is not None and 'ctx_s' not in bufs
+        f8_up = f8 and blk.wi8 is not None and blk.ffn_act == L.ACT_GELU
+        f8_ffn = f8_up and blk.wo28 is not None and 'u_s' not in bufs and self._q8(blk)
         x1_8 = (self._buf('x1_8', M, H, torch.uint8), self._buf('x1_8s', M, 1, torch.float32)) if f8_up else None
         if f8_o:                                   # the attention output as e4m3 + per-token scale (one row pass), then the fp8 GEMM
             c8, cs = self._buf('ctx8', M, H, torch.uint8), self._buf('ctx8s', M, 1, torch.float32)
@@ -1297,7 +1051,7 @@ class TransRecEngine:
         self._wgrad_join()                               # dzp / dv are about to be overwritten
         if ad is None:
             dv = self._buf('dv' + which, M, H, T)
-            if p_drop > 0 and getattr(blk, 'Hv', H) == H:          # one launch writes dv and mask * dv (a4r_ln_bwd's second output; mask index = row * H + col)
+            if p_drop > 0 and blk.Hv == H:          # one launch writes dv and mask * dv (a4r_ln_bwd's second output; mask index = row * H + col)
                 dh = self._buf('dh' + which, M, H, T)
                 L.ln_bwd(dy, v, st, ln.gamma, dv, M=M, dgamma=gg(ln.g_gamma), dbeta=gg(ln.g_beta),
                          dv2=dh, drop2_p=p_drop, drop2_site=site, drop2_seed=seed)
@@ -1492,7 +1246,7 @@ class TransRecEngine:
         dh2, dres2 = self._sub_backward(blk, '2', dx_out, blk.ln2, blk.ad2, blk.pl2, blk.lnn2, bufs, M, ph, blk.site + 2, seed)
         self._dense_wgrad(blk.d_o2, dh2, bufs.get('u_s'), M)
         dx1 = self._buf('dx1', M, H, T)
-        if (self.fp8 and getattr(blk, 'wo2T8', None) is not None and T == torch.bfloat16 and M % 256 == 0 and bufs['upre'].dtype == torch.uint8
+        if (self.fp8 and blk.wo2T8 is not None and T == torch.bfloat16 and M % 256 == 0 and bufs['upre'].dtype == torch.uint8
                 and 'u_s' not in bufs):
             # frozen FFN, both dgrads on e4m3 operands with ONE scale per token row carried through the chain (_build_fp8):
             #   dh2 -> e4m3 + row scale | du = (dh2 W2) * gelu' leaves its GEMM as e4m3 with scale[m] * c_du | dx1 = du W1 + dres2 (bf16 out)
@@ -1528,7 +1282,7 @@ class TransRecEngine:
             dres1 = rfull
         n_tok = self._pk['Mtok'] if self._off(blk) is not None else n_items * blk.S
         dqkv = self._buf_tail0('dqkv', M, 3 * H, T, n_tok)                 # attn_bwd writes the real token rows only
-        if getattr(blk, 'long', False):
+        if blk.long:
             ws = self._buf('attn_ws', bufs['lse'].shape[0], 1, torch.float32)
             L.attn_long_bwd(bufs['qkv'], bufs['ctx_o'], dctx, dqkv, bufs['lse'], ws, n_items, blk.S, blk.nh, blk.dh, 0, H, 2 * H, blk.scale,
                             drop_p=pa, drop_site=blk.site, drop_seed=seed, key_mask=key_mask, causal=blk.causal)
@@ -1569,7 +1323,7 @@ class TransRecEngine:
         """model.py:546-559: last = 0; for each listed hidden state: last = adapter(hidden + last); cls rows of
         com_dense([last_hidden ; last]) -> `cls`."""
         H, T, nb = self.H, self.T, len(self.bert_blocks)
-        if keep and (getattr(self, '_kad_saved_b', None) is None or self._kad_saved_M != M):
+        if keep and (self._kad_saved_b is None or self._kad_saved_M != M):
             self._kad_saved_b = [self._kad_bufs(k, M) for k in self.bert_kads]
             self._kad_saved_M = M
         last = None
@@ -1695,7 +1449,7 @@ class TransRecEngine:
             return xs[-1], Mu
         other = self._buf('sx_b', Mu, E, torch.float32)
         keep = saved is not None
-        if self.sas_kads and keep and (getattr(self, '_kad_saved_s', None) is None or self._kad_saved_Mu != Mu):
+        if self.sas_kads and keep and (self._kad_saved_s is None or self._kad_saved_Mu != Mu):
             self._kad_saved_s = [self._kad_bufs(k, Mu) for k in self.sas_kads]
             self._kad_saved_Mu = Mu
         last = None
@@ -1742,7 +1496,7 @@ class TransRecEngine:
 
     def _attr_table(self, key, src, dst_off_rows, n, into_rows):
         """descriptor table of one a4r_unpack_add launch that adds src blocks scaled by 1 / n_attr (cached per buffer address and item count)"""
-        cache = self.__dict__.setdefault('_attr_tabs', {})
+        cache = self._attr_tabs
         k = (key, src.data_ptr(), n)
         if k not in cache:
             if len(cache) >= 64:                   # ragged histories change n almost every step: keep the table count (and the H2D copies' garbage) bounded
@@ -1915,7 +1669,7 @@ class TransRecEngine:
             if kidx is not None:
                 n_c = kidx[1]
         row_bytes = news[0].numel() * news.element_size() if n_full else 0
-        noise = getattr(self, 'next_noise', None)  # (ViT-MAE: explicit masking noise comes per item of the FULL layout)
+        noise = self.next_noise                    # (ViT-MAE: explicit masking noise comes per item of the FULL layout)
         if noise is not None and n_c is not None:
             noise = noise.to(self.dev, torch.float32).contiguous()
             if noise.dim() != 2 or noise.shape[0] != n_full or (noise.shape[1] * 4) % 16:
@@ -1947,7 +1701,7 @@ class TransRecEngine:
         self._pk = None
         if (hl is not None and hmt is not None and S_step <= self.S0 and type(self) is TransRecEngine and not self.bert_kads and not self.prompt_n
                 and not self.train_emb and not self.fp8 and self.bert_blocks and self.bert_blocks[0].dh in (32, 64) and len(hl) == n_full
-                and not getattr(self.bert_blocks[0], 'long', False)             # (the long attention kernels take no offsets)
+                and not self.bert_blocks[0].long             # (the long attention kernels take no offsets)
                 and skip):
             import numpy as np
             if kidx is not None:
@@ -1985,7 +1739,7 @@ class TransRecEngine:
         M = pad_to(self._pk['Mtok'], 256) if self._pk is not None else pad_to(n_enc * self.S, 256)
         Mu = pad_to(B * (self.Lseq - 1), 128)
         Ipc = pad_to(n_enc, 128)
-        if self._saved_bert is None or self._saved_M != M or self._saved_Mu != Mu or getattr(self, '_saved_Ip', Ipc) != Ipc:
+        if self._saved_bert is None or self._saved_M != M or self._saved_Mu != Mu or self._saved_Ip != Ipc:
             self._saved_Ip = Ipc                   # (the item count changes from step to step when pad slots are left out)
             nb = len(self.bert_blocks)
             self._saved_bert = [self._block_bufs(f'bert.{i}', b, M, False, Mc=Ipc if (self.cls_only and i == nb - 1) else None)
@@ -2026,7 +1780,7 @@ class TransRecEngine:
         outside the layers).  A chunk holding a gradient that only reaches the flat buffer at the very end (a zero-padded scratch
         corner: the reference's 16-wide SASRec adapters) is marked late and goes out after the flush.  None (= the single all-reduce)
         for Compacter, whose PHM chain fills every adapter gradient at the end."""
-        if getattr(self, '_chunks', 0) != 0:
+        if self._chunks != 0:
             return self._chunks
         self._chunks = None
         if self._virtual or not self.OVERLAP_ALLREDUCE:
@@ -2058,7 +1812,7 @@ class TransRecEngine:
 
     def _exchange(self, what):
         """Start the all-reduce of one finished chunk (no-op outside an overlapped data-parallel backward)."""
-        ex = getattr(self, '_exch', None)
+        ex = self._exch
         if ex is None:
             return
         ddp, ch, done, final = ex

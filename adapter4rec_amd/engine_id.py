@@ -27,6 +27,7 @@ def loss_flag(args, arch, use_modal):
 
 
 class IdRecEngine(TransRecEngine):
+    MULTI_ATTR = False
 
     def __init__(self, model, args, arch='sasrec', dtype='bf16', phm_owner=None):
         if dtype == 'fp8':

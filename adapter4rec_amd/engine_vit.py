@@ -16,17 +16,17 @@ The input side is a4r_patchify (im2col + uint8 normalise; ViT-MAE: only the kept
 the Conv2d weight -> a4r_vit_assemble (cls, position rows).  Hidden / attention dropout are 0 in the ViT configs the
 reference loads (google/vit-base-patch16-224, facebook/vit-mae-base) and are required to be 0 here.
 """
-import math
-
 import torch
 
 from . import _lib as L
-from .engine import TransRecEngine, _Adapter, _Block, _Dense, _LN, _Lora, pad_to
+from .engine import TransRecEngine
+from .engine_blocks import _Adapter, _Block, _Dense, _LN, pad_to
 from .cv.vit import vit_geometry
 from .model.modules import AdapterBlock, HyperComplexAdapterBlock
 
 
 class ViTRecEngine(TransRecEngine):
+    MULTI_ATTR = False
     WGRAD_SIDE_OK = False           # the image tower's gradient buffers ping-pong: its weight gradients stay on the main stream
 
     # ------------------------------------------------------------------ build
@@ -72,65 +72,30 @@ class ViTRecEngine(TransRecEngine):
         if self.res32:
             raise NotImplementedError('--residual_dtype fp32 is wired for the text tower (post-LN sub-layers on the one-launch adapter kernels); the pre-LN '
                                       'image tower stores its residual stream v itself in the compute dtype')
-        self.next_noise = None
+        self._mae_step, self._mae_draw = None, 0       # ViT-MAE masking stream: the step it last drew for, draws within that step
         self.bert_blocks = []
         kmod, enc_mod = None, core.encoder
         if type(enc_mod).__name__ == 'VITKAdaptedCVModel':       # model.py:374-404: the wrapper sits where vit.encoder was
             kmod, enc_mod = enc_mod, enc_mod.vit_encoder
         for i, layer in enumerate(enc_mod.layer):
-            b = _Block()
             att = layer.attention.attention
-            for lin in (att.query, att.key, att.value):
-                if type(lin).__name__ not in ('LoRALinear', 'Linear'):
-                    raise NotImplementedError(f'projection module {type(lin).__name__}')
-            b.lora = _Lora.for_block((att.query, att.key, att.value), H, self, self.T)
-            b.H, b.F, b.nh, b.dh, b.S = H, self.F, nh, 64, self.S
-            b.scale = 1.0 / math.sqrt(64)
-            b.wqkv = torch.zeros(3 * H, H, dtype=self.T, device=self.dev)
-            b.wqkvT = torch.zeros(H, 3 * H, dtype=self.T, device=self.dev)
-            b.bqkv = torch.zeros(3 * H, dtype=torch.float32, device=self.dev)
-            self._pack_lora_bias(b, H)
-            b.qkv = tuple(None if type(lin).__name__ == 'LoRALinear' else
-                          _Dense(self, lin.weight, lin.bias, self.T, b.wqkv[sl * H:(sl + 1) * H], b.wqkvT[:, sl * H:(sl + 1) * H],
-                                 b.bqkv[sl * H:(sl + 1) * H])
-                          for sl, lin in enumerate((att.query, att.key, att.value)))
+            b = _Block(self, (att.query, att.key, att.value), H, H, self.F, nh, self.S, self.T, True, L.ACT_GELU)
             d1, b.ad1 = self._vit_so(layer.attention.output)
             d2, b.ad2 = self._vit_so(layer.output)
-            b.d_o = _Dense(self, d1.weight, d1.bias, self.T)
-            b.d_i = _Dense(self, layer.intermediate.dense.weight, layer.intermediate.dense.bias, self.T)
-            b.d_o2 = _Dense(self, d2.weight, d2.bias, self.T)
-            b.wo, b.woT, b.bo = b.d_o.w, b.d_o.wT, b.d_o.b
-            b.wi, b.wiT, b.bi = b.d_i.w, b.d_i.wT, b.d_i.b
-            b.wo2, b.wo2T, b.bo2 = b.d_o2.w, b.d_o2.wT, b.d_o2.b
-            b.train_dense = any(d is not None and d.trainable for d in b.qkv + (b.d_o, b.d_i, b.d_o2))
+            b.set_dense(self, d1, layer.intermediate.dense, d2)
             b.lnA, b.lnB = _LN(layer.layernorm_before, self), _LN(layer.layernorm_after, self)
             b.need_dx = i > 0 or self.train_emb
-            b.T = self.T
             self.bert_blocks.append(b)
         self.vit_ln = _LN(core.layernorm, self)
         fc = enc.cv_proj if self.mae else net.classifier
         if self.E % 64 or fc.out_features != self.E:
             raise NotImplementedError('item head: classifier / cv_proj with embedding_dim % 64 == 0')
-        self.d_fc = _Dense(self, fc.weight, fc.bias, self.T)
-        self.fc_w, self.fc_b = self.d_fc.w, self.d_fc.b
-        self.fc_wT32 = torch.zeros(fc.in_features, fc.out_features, dtype=torch.float32, device=self.dev)
-        if fc.weight.requires_grad:
-            self.add_pack(fc.weight, self.fc_wT32, True)
-        else:
-            self.fc_wT32.copy_(fc.weight.detach().t().float())
+        self._build_head(fc)
         self.cls_only = bool(getattr(self.args, 'cls_only_last', True))      # last layer: only the CLS rows go past attention
         self.bert_trains = any(p.requires_grad for p in enc_mod.parameters())
-        self.bert_kads, self.bert_klist, self.d_com = [], [], None
-        if kmod is not None:
-            nb = len(self.bert_blocks)
-            self.bert_klist = [int(k) for k in kmod.k_adapter_num_list]
-            if any(k < 1 or k > nb for k in self.bert_klist):
-                raise ValueError(f'--k_adapter_bert_list {self.bert_klist} outside 1..{nb}')
-            if self.fp8:
-                raise NotImplementedError('K-Adapter on the fp8 image tower')
-            self.bert_kads = [self._make_kadapter(a, H, self.S, self.T, 6000 + 64 * j) for j, a in enumerate(kmod.bert_adapter_list)]
-            self.d_com = _Dense(self, kmod.com_dense.weight, kmod.com_dense.bias, self.T)
-            self.cls_only = False                      # the adapters attend over all tokens of the last layer's output
+        if kmod is not None and self.fp8:
+            raise NotImplementedError('K-Adapter on the fp8 image tower')
+        self._build_item_kads(kmod)
 
     def _vit_so(self, mod):
         """(dense Linear, adapter or None) of a plain or wrapped ViTSelfOutput / ViTOutput."""
@@ -146,7 +111,7 @@ class ViTRecEngine(TransRecEngine):
 
     # ------------------------------------------------------------------ buffers
     def _block_bufs(self, tag, blk, M, shared, Mc=None):
-        if not hasattr(blk, 'lnA'):
+        if blk.lnA is None:
             return super()._block_bufs(tag, blk, M, shared, Mc)
         pre = tag if not shared else tag.split('.')[0] + '.shared'
         T, H, F = blk.T, blk.H, blk.F
@@ -184,7 +149,7 @@ class ViTRecEngine(TransRecEngine):
             L.gemm_nt(dense_in, w, out, bias=bias, R1=resid, M=M, **sk)
             return
         h, zp, z = bufs['h' + k], bufs['zp' + k], bufs['z' + k]
-        if getattr(ad, 'parallel', False):    # model.py:165-179: dense(u) + x + [fc_up(act(fc_down(x))) + x], the adapter reads the sub-layer INPUT x
+        if ad.parallel:    # model.py:165-179: dense(u) + x + [fc_up(act(fc_down(x))) + x], the adapter reads the sub-layer INPUT x
             L.gemm_nt(resid, ad.wd, z, bias=ad.bd, C2=zp, act=ad.act, M=M)
             L.gemm_nt(z, ad.wu, h, bias=ad.bu, R1=resid, R2=resid, M=M)
             L.gemm_nt(dense_in, w, out, bias=bias, R1=h, M=M, **sk)
@@ -200,7 +165,7 @@ class ViTRecEngine(TransRecEngine):
         """The one-launch adapter + residual + LayerNorm kernels (a4r_adapter_fused.hip) serve the pre-LN tower too: v = the residual
         stream after the sub-layer, y = the NEXT LayerNorm's output (LN_after for the attention sub-layer, the next layer's LN_before
         for the FFN sub-layer).  Serial placement, bf16, bottleneck 64."""
-        if ad is None or getattr(ad, 'parallel', False):
+        if ad is None or ad.parallel:
             return False
         return (self._fuse_bwd if bwd else self._fuse)(blk, ad, t)
 
@@ -306,7 +271,7 @@ class ViTRecEngine(TransRecEngine):
         dzp = self._buf('dzp', M, ad.dp, T)
         L.gemm_nt(dy, ad.wuT, dzp, Pre=zp, dact=ad.act, M=M)
         dh = self._buf('dh' + k, M, H, T)
-        if getattr(ad, 'parallel', False):
+        if ad.parallel:
             L.gemm_nt(dzp, ad.wdT, dh, R1=dy, R2=dy, M=M)
             self._adapter_wgrads(ad, dy, z, dzp, x_in, M)
             if ad.g_bu is not None:
@@ -424,7 +389,7 @@ class ViTRecEngine(TransRecEngine):
             # the stream instead of replaying the first run's masks, and the ranks of a data-parallel job mask differently (as
             # DeviceTrainSampler.set_epoch does for the negatives)
             step = self.step_count + 1
-            if getattr(self, '_mae_step', None) != step:
+            if self._mae_step != step:
                 self._mae_step, self._mae_draw = step, 0
             self._mae_draw += 1
             import torch.distributed as dist
