@@ -14,7 +14,10 @@ element index every kernel family hands it:
     kind 'attn_item'  item tower probabilities [items, heads, S, S], pair = item * heads + head:
                          head dim <= 16:  ((pair * S + q) * S + k)                 a4r_attn_small.hip:52
                          S <= 32:         ((pair * 32 + q) * 32 + k)               a4r_attn.hip:151
-                         else:            ((pair * 256 + q) << 8) + k              a4r_attn_long.hip:151
+                         else:            ((pair * 256 + q) << 8) + k              a4r_attn_long.h: drop_idx
+                      The index follows the KERNEL FAMILY, not the shape: the wide heads (128 / 256) at S <= 32 run a4r_attn.hip's kernels and draw
+                      its index; a4r_attn_long_* accept any S <= 256 and draw theirs at S <= 32 as well (long_kernels=True says so); head width
+                      128 there is the same kernels' fp32 instantiation.
     kind 'attn_user'  SASRec block probabilities [users, heads, T, T]:  (((user * heads + head) * 32 + q) << 5) + k       a4r_sasrec.hip:202
                       (T > 32, the long attention kernels:               (((user * heads + head) * 256 + q) << 8) + k)
     kind 'rows_user'  SASRec block rows [users, T, E]:                   (user * 32 + t) * E + c                           a4r_sasrec.hip:217,269
@@ -80,7 +83,7 @@ class DropoutStream:
         self.sasrec_fused = bool(sasrec_fused)      # one launch per SASRec block (a4r_sasrec.hip: 32 rows per user) or the multi-launch user tower
         self.used = []                              # (GEMM epilogues on [users * T, E] rows: plain 'rows'); engine._sas_fused_ok() says which ran
 
-    def mask(self, kind, site, x, p, head_dim=None):
+    def mask(self, kind, site, x, p, head_dim=None, long_kernels=None):
         self.used.append((kind, int(site)))
         shp = tuple(x.shape)
         if p <= 0:
@@ -104,7 +107,9 @@ class DropoutStream:
         elif kind == 'attn_item':
             i, h, q, k = np.meshgrid(*[np.arange(n, dtype=np.uint64) for n in shp], indexing='ij')
             pair, S = i * np.uint64(shp[1]) + h, shp[2]
-            if head_dim is not None and head_dim <= 16:
+            if long_kernels if long_kernels is not None else (S > 32):          # (None: the engine's dispatch, by S)
+                e = ((pair * np.uint64(256) + q) << np.uint64(8)) + k
+            elif head_dim is not None and head_dim <= 16:
                 e = (pair * np.uint64(S) + q) * np.uint64(S) + k
             elif S <= 32:
                 e = (pair * np.uint64(32) + q) * np.uint64(32) + k
