@@ -30,7 +30,7 @@ EXPORTS = [
     'a4r_sasrec_block_fwd', 'a4r_sasrec_block_bwd', 'a4r_scatter_rows_fill', 'a4r_attn_long_fwd', 'a4r_attn_long_bwd', 'a4r_patchify', 'a4r_vit_assemble', 'a4r_resample_u8', 'a4r_embed_bwd', 'a4r_mae_keep_indices',
     'a4r_encoder_layer_fwd', 'a4r_encoder_layer_bwd', 'a4r_id_index', 'a4r_id_index_ws_ints', 'a4r_id_grad_sum',
     'a4r_topk_items', 'a4r_grad_sumsq', 'a4r_adamw_step',
-    'a4r_score_ce_ranges', 'a4r_score_ce_fwd', 'a4r_score_ce_bwd_rows', 'a4r_score_ce_bwd_items',
+    'a4r_score_ce_ranges', 'a4r_score_ce_fwd', 'a4r_score_ce_bwd_rows', 'a4r_score_ce_bwd_items', 'a4r_id_sample',
 ]
 ID_SUM_CHUNK = 16          # A4R_ID_SUM_CHUNK (include/a4r.h)
 TOPK_MAX_K = 256           # A4R_TOPK_MAX_K (include/a4r.h)
@@ -38,6 +38,8 @@ TOPK_E = (64, 128, 256, 512)
 GRAD_NORM_PARTS = 1024     # A4R_GRAD_NORM_PARTS (include/a4r.h)
 SCORE_CE_E = TOPK_E         # table widths of the cross-entropy head (a4r_score_ce_*)
 SCORE_CE_MAX_RANGES = 32   # A4R_SCORE_CE_MAX_RANGES (include/a4r.h)
+SAMPLE_MAX_L = 256         # a4r_id_sample: the longest sequence row (include/a4r.h)
+SAMPLE_SITE = 7001         # A4R_SAMPLE_SITE (csrc/a4r_common.h): the hash site of a4r_id_sample's draws
 
 
 class GemmArgs(C.Structure):
@@ -869,3 +871,33 @@ def eval_rank(prec, item_emb, target, hist_ptr, hist_idx, rank):
     require_gpu(prec, item_emb, target, hist_ptr, hist_idx, rank)
     _check(lib().a4r_eval_rank(_stream(), _p(prec), _p(item_emb), _p(target), _p(hist_ptr), _p(hist_idx), _p(rank),
                                C.c_int(prec.shape[0]), C.c_int(item_emb.shape[0]), C.c_int(prec.shape[1])), 'a4r_eval_rank')
+
+
+def id_sample(seqs, rows, item_num, seed, draw, negatives, ids, log_mask, err):
+    """a4r_id_sample: the training batch of the users rows [B] (int32 rows of seqs, int32 [n_users, L] left-padded with 0) -> ids int64 [B, L, 2]
+    (positives | one negative per real position except the last), log_mask fp32 [B, L - 1], err int32 [1] (out-of-range rows and users without a
+    candidate, overwritten).  The negative of (user row, position) is a pure function of (seed, draw, row, position) (include/a4r.h);
+    negatives false: column 1 stays 0 and nothing is drawn.  Argument errors raise ValueError before the call."""
+    for name, t in (('seqs', seqs), ('rows', rows), ('err', err)):
+        if t.dtype != torch.int32 or not t.is_contiguous():
+            raise ValueError(f'id_sample: {name} must be contiguous int32')
+    if seqs.dim() != 2 or rows.dim() != 1:
+        raise ValueError(f'id_sample: seqs [n_users, L] and rows [B] expected, got {tuple(seqs.shape)} and {tuple(rows.shape)}')
+    n_users, L = seqs.shape
+    B = rows.numel()
+    if not 2 <= L <= SAMPLE_MAX_L:
+        raise ValueError(f'id_sample: L = {L} outside 2 .. {SAMPLE_MAX_L}')
+    if B < 1 or n_users < 1 or not 1 <= int(item_num) < 2 ** 31:
+        raise ValueError(f'id_sample: B = {B} rows, n_users = {n_users}, item_num = {item_num}: need B >= 1, n_users >= 1, 1 <= item_num < 2^31')
+    if not 0 <= int(draw) < 2 ** 24:
+        raise ValueError(f'id_sample: draw = {draw} outside 0 .. 2^24 - 1')
+    if ids.dtype != torch.int64 or not ids.is_contiguous() or tuple(ids.shape) != (B, L, 2):
+        raise ValueError(f'id_sample: ids must be contiguous int64 [{B}, {L}, 2]')
+    if log_mask.dtype != torch.float32 or not log_mask.is_contiguous() or tuple(log_mask.shape) != (B, L - 1):
+        raise ValueError(f'id_sample: log_mask must be contiguous fp32 [{B}, {L - 1}]')
+    if err.numel() != 1:
+        raise ValueError('id_sample: err must hold one int32')
+    require_gpu(seqs, rows, ids, log_mask, err)
+    _check(lib().a4r_id_sample(_stream(), _p(seqs), C.c_int(n_users), C.c_int(L), _p(rows), C.c_int(B), C.c_int(int(item_num)),
+                               C.c_uint64(int(seed) & (2 ** 64 - 1)), C.c_uint64(int(draw)), C.c_int(int(bool(negatives))),
+                               _p(ids), _p(log_mask), _p(err)), 'a4r_id_sample')

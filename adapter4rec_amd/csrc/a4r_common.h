@@ -297,6 +297,9 @@ A4R_DEV uint64_t a4r_hash64(uint64_t seed, uint32_t site, uint64_t idx) {
     const uint32_t hi = a4r_mix32((c * 2u + 1u) ^ s1 ^ lo);
     return ((uint64_t)hi << 32) | lo;
 }
+// The hash's other user: a4r_id_sample draws a training batch's negatives from a4r_hash64(seed, A4R_SAMPLE_SITE, counter).  The dropout sites
+// are 999, 16 i + {0, 1, 2}, 4000 and 4096 + 16 j + {0, 1, 2} (engine.py): 7001 is none of them.
+#define A4R_SAMPLE_SITE 7001u
 A4R_DEV bool dropout_keep(uint64_t seed, uint32_t site, uint64_t e, uint32_t thr16) {
     uint64_t h = a4r_hash64(seed, site, e >> 2);
     return ((uint32_t)(h >> (16 * (e & 3))) & 0xffffu) >= thr16;

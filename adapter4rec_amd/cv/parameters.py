@@ -34,6 +34,9 @@ def parse_args(argv=None):
     p.add_argument('--use_scale', type=str, default='half')       # reference: fp16 autocast; here the engine's bf16 storage / fp32 accumulate
     p.add_argument('--n_tokens', type=int, default=10)
     p.add_argument('--num_workers', type=int, default=12)
+    p.add_argument('--device_sampler', type=int, default=0,
+                   help='--item_tower id: 1 draws the training batches on the GPU (data_utils.DeviceIdSampler, one a4r_id_sample launch per batch) '
+                        'instead of BuildTrainDataset + DataLoader; same distribution, not the same draws')
     p.add_argument('--load_ckpt_name', type=str, default='None')
     p.add_argument('--topk', type=int, default=10)                     # --mode recommend: items per user
     p.add_argument('--recommend_out', type=str, default=None)          # --mode recommend: output file (default <model_dir>/recommend_<load_ckpt_name>.tsv)

@@ -16,7 +16,7 @@ import torch
 import torch.distributed as dist
 from torch.utils.data import DataLoader
 
-from ..data_utils.dataset import BuildTrainDataset
+from ..data_utils.dataset import BuildTrainDataset, DeviceIdSampler
 from ..data_utils.utils import get_checkpoint, para_and_log, report_time_eval, report_time_train, save_model, setuplogger
 from ..ddp import FlatDDP, any_rank
 from ..inject import freeze_all
@@ -116,9 +116,16 @@ def _collate(batch):
     return torch.stack([b[0] for b in batch]), torch.stack([b[1] for b in batch])
 
 
+SAMPLER_SEED = 123456          # --device_sampler 1: one constant for every rank (a draw is keyed by the GLOBAL user row, include/a4r.h: a4r_id_sample)
+
+
 def train(args, use_modal, local_rank, Log_file, Log_screen, model_dir, start_time):
     if not use_modal:
         check_id_flags(args)
+    device_sampler = bool(getattr(args, 'device_sampler', 0))
+    if device_sampler and use_modal:
+        raise NotImplementedError('--device_sampler 1 with an item encoder (--item_tower modal): the image records live on the host; '
+                                  'the device sampler draws ID batches (--item_tower id)')
     cv_model = load_backbone(args, Log_file) if use_modal else None       # --item_tower id: no backbone, no image database
     before_keys, before_name2id = read_images(os.path.join(args.root_data_dir, args.dataset, args.images))
     item_num, item_id_to_keys, users_train, users_valid, users_test, hist_valid, hist_test = read_behaviors(
@@ -134,7 +141,13 @@ def train(args, use_modal, local_rank, Log_file, Log_screen, model_dir, start_ti
     else:
         train_dataset = Build_Lmdb_Dataset(users_train, item_num, args.max_seq_len, db, item_id_to_keys, args.CV_resize, device=f'cuda:{local_rank}', host=host)
     sampler = torch.utils.data.distributed.DistributedSampler(train_dataset)
-    if not use_modal and args.num_workers > 0:
+    dev_sampler = train_dl = None
+    if device_sampler:
+        # the batches are drawn on the GPU, one launch each (no DataLoader, no per-step upload); the DistributedSampler still shards and shuffles
+        # the users.  --loss ce reads no negative: none is drawn
+        dev_sampler = DeviceIdSampler(users_train, item_num, args.max_seq_len, torch.device('cuda', local_rank), seed=SAMPLER_SEED,
+                                      negatives=args.loss != 'ce')
+    elif not use_modal and args.num_workers > 0:
         def worker_init(worker_id):                                    # (the worker seeding of the image path below)
             seed = torch.initial_seed() % 2 ** 31 + worker_id + dist.get_rank()
             random.seed(seed)
@@ -169,13 +182,15 @@ def train(args, use_modal, local_rank, Log_file, Log_screen, model_dir, start_ti
         Log_file.info('epoch {} start'.format(now_epoch))
         loss, batch_index, need_break = 0.0, 1, False
         model.train()
-        train_dl.sampler.set_epoch(now_epoch)
+        sampler.set_epoch(now_epoch)
+        if dev_sampler is not None:
+            dev_sampler.set_epoch(now_epoch, list(iter(sampler)))
         # --num_workers 0: Build_Lmdb_Dataset draws its negatives from Python's `random` in THIS process, and the checkpoint holds the torch RNG state
         # only (utils.py:109-115): the epoch's stream is re-seeded from the torch generator, so a resumed run draws the negatives the uninterrupted
         # run would have.  With a worker pool the draw below is kept (both runs consume the same generator state) and the workers' streams come from
         # the iterator's base seed (worker_init above) -- the text entry point's arrangement.
         random.seed(int(torch.randint(0, 2 ** 31 - 1, (1,)).item()))
-        for sample_items, log_mask in train_dl:
+        for sample_items, log_mask in (train_dl if dev_sampler is None else dev_sampler.batches(args.batch_size)):
             if not use_modal:
                 sample_items = sample_items.view(-1)                   # int64 ids on the host (run_adapter.py:581-584); the engine uploads them
             elif host:

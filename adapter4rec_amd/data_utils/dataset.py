@@ -6,6 +6,8 @@ import numpy as np
 import torch
 from torch.utils.data import Dataset
 
+from .. import _lib as L
+
 
 class BuildTrainDataset(Dataset):
     """dataset.py:10-49: user -> (item contents [L, 2, 2*words] int64, log_mask [L-1] fp32); L = max_seq_len + 1.
@@ -88,6 +90,83 @@ class DeviceTrainSampler:
         neg = torch.where(need, neg, torch.zeros_like(neg))
         ids = torch.stack([seq, neg], 2).reshape(-1)                       # [B, L, 2] -> rows (b, l, pos|neg)
         return self.content[ids].contiguous(), log_mask
+
+
+class DeviceIdSampler:
+    """The ID tower's BuildTrainDataset + DataLoader on the device (--item_tower id --device_sampler 1): every user's training sequence lives on
+    the GPU as one left-padded int32 [U, L] table and a batch is ONE launch of a4r_id_sample (include/a4r.h) -- no per-step host-to-device copy,
+    no host read.  Same layout and distribution as dataset.py:24-49: ids [B, L, 2] = (sequence | one negative per real position except the last,
+    uniform over 1..item_num minus the user's own items), log_mask = [0]*pad + [1]*(len - 1); without the reference's rejection loop.  The
+    negative of (user row, position) is a pure function of (seed, draw = epoch, row, position): it depends on no batch composition, rank or step
+    count, so a resumed run draws what the uninterrupted run drew with no sampler state in the checkpoint.  negatives=False (--loss ce, whose
+    head reads no negative): the negatives column is all zeros and nothing is drawn."""
+
+    def __init__(self, u2seq, item_num, max_seq_len, device, seed=0, negatives=True):
+        self.L, self.item_num, self.device = max_seq_len + 1, int(item_num), torch.device(device)
+        self.seed, self.negatives, self.draw, self.order = int(seed), bool(negatives), 0, None
+        if not 2 <= self.L <= L.SAMPLE_MAX_L:
+            raise ValueError(f'DeviceIdSampler: max_seq_len + 1 = {self.L} outside 2 .. {L.SAMPLE_MAX_L}')
+        users = sorted(u2seq) if isinstance(u2seq, dict) else list(range(len(u2seq)))
+        if not users:
+            raise ValueError('DeviceIdSampler: no user sequences')
+        tab = np.zeros((len(users), self.L), dtype=np.int32)
+        for r, u in enumerate(users):
+            seq = list(u2seq[u])
+            if len(seq) > self.L:
+                raise ValueError(f'DeviceIdSampler: user {u} has {len(seq)} items, the table row holds max_seq_len + 1 = {self.L}')
+            if seq and not (1 <= min(seq) and max(seq) <= self.item_num):
+                raise ValueError(f'DeviceIdSampler: user {u} has item ids outside 1 .. {self.item_num}')
+            if self.negatives and self.item_num - len(set(seq)) < 1:
+                raise ValueError(f'DeviceIdSampler: user {u} holds all {self.item_num} items: no negative to draw')
+            if seq:
+                tab[r, self.L - len(seq):] = seq
+        self.row_of = {u: r for r, u in enumerate(users)}
+        self.seqs = torch.from_numpy(tab).to(self.device)
+        self.err = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self._err_pending, self._err_free = [], []           # (pinned host word, event) per batch not yet checked; spare words
+
+    def set_epoch(self, epoch, order):
+        """order: the epoch's user ids as the DistributedSampler yields them (sharding and shuffling stay the DataLoader path's), uploaded once;
+        draw = epoch."""
+        if not 0 <= int(epoch) < 2 ** 24:
+            raise ValueError(f'DeviceIdSampler: epoch {epoch} outside 0 .. 2^24 - 1')
+        self.draw = int(epoch)
+        rows = np.fromiter((self.row_of[int(u)] for u in order), dtype=np.int32)
+        self.order = torch.from_numpy(rows).to(self.device)
+
+    def _raise_pending(self):
+        """The error words of earlier batches whose copies to pinned host memory have landed (queried, never waited for)."""
+        while self._err_pending and (self._err_pending[0][1] is None or self._err_pending[0][1].query()):
+            host, _ = self._err_pending.pop(0)
+            bad = int(host[0])
+            self._err_free.append(host)
+            if bad:
+                raise IndexError(f'DeviceIdSampler: {bad} rows of an earlier batch outside the sequence table or without a candidate negative')
+
+    def _post_err(self):
+        if not self.err.is_cuda:                    # (host-logic tests: a CPU stand-in of the library)
+            self._err_pending.append((self.err.clone(), None))
+            return
+        host = self._err_free.pop() if self._err_free else torch.zeros(1, dtype=torch.int32).pin_memory()
+        host.copy_(self.err, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        self._err_pending.append((host, ev))
+
+    def batches(self, batch_size):
+        """-> (ids.view(-1) int64 [B * L * 2], log_mask fp32 [B, L - 1]) device tensors over slices of the epoch's order; the last one is short
+        (no drop_last).  Every batch gets tensors of its own: the engine keeps the step's log_mask until its backward."""
+        if self.order is None:
+            raise RuntimeError('DeviceIdSampler.batches: call set_epoch(epoch, order) first')
+        for i in range(0, self.order.numel(), batch_size):
+            self._raise_pending()
+            rows = self.order[i:i + batch_size]
+            ids = torch.empty(rows.numel(), self.L, 2, dtype=torch.int64, device=self.device)
+            log_mask = torch.empty(rows.numel(), self.L - 1, dtype=torch.float32, device=self.device)
+            L.id_sample(self.seqs, rows, self.item_num, self.seed, self.draw, self.negatives, ids, log_mask, self.err)
+            self._post_err()
+            yield ids.view(-1), log_mask
+        self._raise_pending()
 
 
 class BuildEvalDataset(Dataset):

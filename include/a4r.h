@@ -547,6 +547,24 @@ int a4r_id_index_ws_ints(int n, int item_num);
 int a4r_id_grad_sum(void* stream, const float* src, int ld_src, const int32_t* slots, const int32_t* ptr, const int32_t* uniq,
                     const int32_t* n_uniq, int n, float* grad, int ldg, int E);
 
+/* The ID tower's training batch drawn on the device (--device_sampler 1; new export, ABI 411 kept: no existing argument list changes): what
+ * BuildTrainDataset(use_modal=False) and the runner's .view(-1) hand the engine (Downstream/Text/data_utils/dataset.py:24-49), for the B users rows[b].
+ *   seqs int32 [n_users, L]: row u = user u's training sequence, left-padded with 0 (L = max_seq_len + 1); rows int32 [B], repeats and any order allowed.
+ *   ids int64 [B, L, 2]: ids[b, l, 0] = seqs[rows[b], l]; ids[b, l, 1] = the negative of position l when l < L-1 and seqs[rows[b], l] != 0, else 0
+ *       (the pad slots and the last slot stay 0: [0]*pad + negs + [0]).  log_mask fp32 [B, L-1]: 1.0f where seqs[rows[b], l] != 0, else 0.0f.
+ *   The negative of (user row u, position l) is a pure function of (seed, draw, u, l) -- no rejection loop, nothing depends on the batch:
+ *       D = the distinct non-zero ids of seqs[u] ascending (signed order), d = |D|, m = item_num - d;
+ *       h = a4r_hash64(seed, 7001, (draw << 40) | ((uint64_t)u << 8) | l)   (the dropout hash of csrc/a4r_common.h at site A4R_SAMPLE_SITE = 7001);
+ *       x = ((h * m) >> 64) + 1, the high half of the 64 x 64-bit product; then for every s in D ascending: if (x >= s) ++x; the negative is x.
+ *     x is uniform over 1 .. item_num minus the user's own items up to a bias of m / 2^64: the reference's distribution, without its loop.
+ *   negatives == 0 (--loss ce, whose head reads no negative): column 1 is all zeros, nothing is sorted or drawn.
+ *   *err (overwritten): the batch rows b whose rows[b] lies outside [0, n_users) -- written as rows of pads: ids 0, log_mask 0, seqs not read --
+ *       plus, when negatives != 0, the batch rows whose user has m < 1 (positives and log_mask written, negatives 0).
+ * A4R_EINVAL before any launch: a NULL pointer, L outside 2 .. 256, B < 1, n_users < 1, item_num < 1, draw >= 2^24.  One launch, one wave per
+ * batch row: the sequence sorted in LDS by rank counting.  Integer work only; the one atomic is the integer add on *err. */
+int a4r_id_sample(void* stream, const int32_t* seqs, int n_users, int L, const int32_t* rows, int B, int item_num,
+                  uint64_t seed, uint64_t draw, int negatives, int64_t* ids, float* log_mask, int32_t* err);
+
 /* ONE post-LN encoder layer per call (ABI 409; SURVEY 8(b) `encoder_layer_fwd / bwd`): HF BertLayer with the reference's serial Houlsby wrappers on
  * both sub-layers (Downstream/Text/model/model.py:292-297 on attention.output and output, injected at run.py:452-465), frozen backbone.  The call
  * ENQUEUES the launches the per-kernel path issues for such a layer, in the same order with the same arguments -- results are bit-identical to
