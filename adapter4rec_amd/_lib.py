@@ -22,16 +22,6 @@ Q8_OFF, Q8_STEP = 0.1289, 0.0049326
 EVAL_MAX_HISTORY = 264         # A4R_EVAL_MAX_HISTORY (include/a4r.h)
 ACT_BY_NAME = {'none': 0, 'relu': 1, 'RELU': 1, 'gelu': 2, 'GELU': 2, 'gelu_new': 3, 'leaky_relu': 4}
 
-EXPORTS = [
-    'a4r_version', 'a4r_gemm_nt', 'a4r_gemm_tn', 'a4r_gemm_tn_bias', 'a4r_gemm_tn_multi', 'a4r_gemm_tn2', 'a4r_colsum', 'a4r_attn_fwd', 'a4r_attn_bwd', 'a4r_embed_ln',
-    'a4r_ln_fwd', 'a4r_ln_bwd', 'a4r_gather_rows', 'a4r_scatter_rows', 'a4r_rows_idx_copy', 'a4r_act_bwd_f32', 'a4r_score_bce_fwd',
-    'a4r_score_bce_bwd', 'a4r_emb_grad_add_inputs', 'a4r_take_inputs', 'a4r_adam_step', 'a4r_pack_matrices',
-    'a4r_eval_rank', 'a4r_dropout_apply', 'a4r_gemm_variant', 'a4r_gemm_tail_plan', 'a4r_gemm_tail_max', 'a4r_gemm_rows_256', 'a4r_adapter_ln_fwd', 'a4r_adapter_ln_bwd', 'a4r_ln_fwd_fp8', 'a4r_ln_fwd_sum', 'a4r_quant_rows_fp8', 'a4r_lora_merge', 'a4r_lora_merge_batch', 'a4r_lora_bwd_fused', 'a4r_lora_bwd_fused_ws_floats', 'a4r_phm_build', 'a4r_phm_bwd', 'a4r_unpack_add', 'a4r_memset_zero',
-    'a4r_sasrec_block_fwd', 'a4r_sasrec_block_bwd', 'a4r_scatter_rows_fill', 'a4r_attn_long_fwd', 'a4r_attn_long_bwd', 'a4r_patchify', 'a4r_vit_assemble', 'a4r_resample_u8', 'a4r_embed_bwd', 'a4r_mae_keep_indices',
-    'a4r_encoder_layer_fwd', 'a4r_encoder_layer_bwd', 'a4r_id_index', 'a4r_id_index_ws_ints', 'a4r_id_grad_sum',
-    'a4r_topk_items', 'a4r_grad_sumsq', 'a4r_adamw_step',
-    'a4r_score_ce_ranges', 'a4r_score_ce_fwd', 'a4r_score_ce_bwd_rows', 'a4r_score_ce_bwd_items', 'a4r_id_sample',
-]
 ID_SUM_CHUNK = 16          # A4R_ID_SUM_CHUNK (include/a4r.h)
 TOPK_MAX_K = 256           # A4R_TOPK_MAX_K (include/a4r.h)
 TOPK_E = (64, 128, 256, 512)
@@ -104,6 +94,93 @@ class AddDesc(C.Structure):
     _fields_ = [('src', C.c_void_p), ('dst_off', C.c_int64), ('rows', C.c_int32), ('cols', C.c_int32), ('ld', C.c_int32), ('alpha', C.c_float)]
 
 
+class TnProb(C.Structure):
+    _fields_ = [('X', C.c_void_p), ('Y', C.c_void_p), ('C', C.c_void_p), ('xsum', C.c_void_p),
+                ('ldx', C.c_int32), ('ldy', C.c_int32), ('ldc', C.c_int32), ('P', C.c_int32), ('Q', C.c_int32), ('pad_', C.c_int32)]
+
+
+class LoraDesc(C.Structure):
+    _fields_ = [('W', C.c_void_p), ('A', C.c_void_p), ('B', C.c_void_p), ('dst', C.c_void_p), ('dstT', C.c_void_p),
+                ('scaling', C.c_float), ('ld', C.c_int32), ('ldT', C.c_int32), ('out_f', C.c_int32), ('in_f', C.c_int32), ('r', C.c_int32)]
+
+
+# The C boundary, declared once: name -> (restype, argtypes) for every export of include/a4r.h, installed by lib().  ctypes then checks the
+# number and the kind of every argument of every call (tests/test_abi_cpu.py compares this table and the mirrors above with the header).
+# Pointers to host structs are POINTER(mirror); device pointers, descriptor tables on the device among them, are c_void_p.
+_P, _I, _L, _U32, _U64, _F, _LONG, _SZ = C.c_void_p, C.c_int, C.c_int64, C.c_uint32, C.c_uint64, C.c_float, C.c_long, C.c_size_t
+_DROP = (_F, _U32, _U64)            # a dropout's (p, site, seed)
+SIGNATURES = {
+    'a4r_version': (_I, ()),
+    'a4r_gemm_nt': (_I, (_P, C.POINTER(GemmArgs))),
+    'a4r_gemm_tail_plan': (_I, (_I, _I, _P, _P)),
+    'a4r_gemm_tail_max': (_I, (_I,)),
+    'a4r_gemm_rows_256': (_I, (_I, _I)),
+    'a4r_gemm_variant': (_I, (_I,)),
+    'a4r_gemm_tn': (_I, (_P, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I)),
+    'a4r_gemm_tn_bias': (_I, (_P, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _P)),
+    'a4r_gemm_tn_multi': (_I, (_P, C.POINTER(TnProb), _I, _I, _I)),
+    'a4r_sasrec_block_fwd': (_I, (_P, C.POINTER(SasrecBlock), _P, _P, _P, _I, _I, _I)),
+    'a4r_sasrec_block_bwd': (_I, (_P, C.POINTER(SasrecBlock), _P, _P, _P, _P, _I, _I, _I)),
+    'a4r_gemm_tn2': (_I, (_P,) + (_P, _I, _P, _I, _P, _I, _I, _I) * 2 + (_I, _I, _P, _P)),
+    'a4r_colsum': (_I, (_P, _P, _I, _P, _I, _I, _I)),
+    'a4r_adapter_ln_fwd': (_I, (_P, _P, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _F, _I, _P, _P, _P, _I, _P, _I, _P, _I, _I, _I, _I,
+                                _P, _I, _P, _P, _I, _P, _I, _I)),
+    'a4r_adapter_ln_bwd': (_I, (_P, _P, _I, _P, _I, _P, _P, _P, _I, _P, _I, _P, _P, _I, _P, _I, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I) + _DROP + (_P, _I, _P)),
+    'a4r_attn_fwd': (_I, (_P, C.POINTER(AttnArgs))),
+    'a4r_attn_bwd': (_I, (_P, C.POINTER(AttnArgs))),
+    'a4r_attn_long_fwd': (_I, (_P, C.POINTER(AttnArgs), _P)),
+    'a4r_attn_long_bwd': (_I, (_P, C.POINTER(AttnArgs), _P, _P)),
+    'a4r_patchify': (_I, (_P, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I)),
+    'a4r_vit_assemble': (_I, (_P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I)),
+    'a4r_mae_keep_indices': (_I, (_P, _P, _P, _I, _I, _I, _U64, _U32)),
+    'a4r_resample_u8': (_I, (_P, _P, _P, _P, _P, _I, _LONG, _I, _I, _LONG)),
+    'a4r_embed_ln': (_I, (_P, _P, _I, _P, _P, _P, _P, _P, _F, _P, _I, _I, _I, _I, _I, _I, _I) + _DROP + (_P, _P, _P)),
+    'a4r_embed_bwd': (_I, (_P, _P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I)),
+    'a4r_ln_fwd': (_I, (_P, _P, _I, _P, _I, _P, _P, _F, _P, _I, _P, _I, _I, _I) + _DROP),
+    'a4r_ln_fwd_sum': (_I, (_P, _P, _I, _P, _I, _P, _I, _P, _P, _F, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I)),
+    'a4r_ln_fwd_fp8': (_I, (_P, _P, _I, _P, _I, _P, _P, _F, _P, _I, _P, _I, _P, _P, _I, _I, _I)),
+    'a4r_quant_rows_fp8': (_I, (_P, _P, _I, _P, _I, _P, _I, _I, _I)),
+    'a4r_ln_bwd': (_I, (_P, _P, _I, _P, _I, _P, _I, _P, _P, _P, _I, _P, _I, _P, _P, _P, _I, _I, _I) + _DROP + (_P, _I) + _DROP),
+    'a4r_gather_rows': (_I, (_P, _P, _I, _P, _I, _I, _I, _I, _I)),
+    'a4r_scatter_rows': (_I, (_P, _P, _I, _P, _I, _I, _I, _I, _I)),
+    'a4r_rows_idx_copy': (_I, (_P, _P, _L, _P, _L, _P, _I, _L, _I)),
+    'a4r_scatter_rows_fill': (_I, (_P, _P, _I, _P, _I, _I, _I, _I, _I, _I)),
+    'a4r_dropout_apply': (_I, (_P, _P, _I, _P, _I, _I, _I, _I) + _DROP),
+    'a4r_act_bwd_f32': (_I, (_P, _P, _P, _P, _L, _I)),
+    'a4r_score_bce_fwd': (_I, (_P,) * 7 + (_I,) * 4),
+    'a4r_score_bce_bwd': (_I, (_P,) * 7 + (_F, _P, _P, _P) + (_I,) * 4),
+    'a4r_emb_grad_add_inputs': (_I, (_P, _P, _I, _P, _I, _I, _I)),
+    'a4r_take_inputs': (_I, (_P, _P, _P, _I, _I, _I, _I)),
+    'a4r_adam_step': (_I, (_P, _P, _P, _P, _P, _L, _P, _P, _I, _P, _I, _F, _F, _F, _F)),
+    'a4r_grad_sumsq': (_I, (_P, _P, _L, _F, _P)),
+    'a4r_adamw_step': (_I, (_P, _P, _P, _P, _P, _L, _P, _P, _I, _P, _I, _F, _F, _F, _F, _P, _I, _P, _F, _P)),
+    'a4r_pack_matrices': (_I, (_P, _P, _P, _I, _I, _I)),
+    'a4r_lora_merge': (_I, (_P, _P, _P, _P, _F, _P, _I, _P, _I, _I, _I, _I, _I)),
+    'a4r_lora_merge_batch': (_I, (_P, _P, _I, _I, _I)),
+    'a4r_lora_bwd_fused': (_I, (_P, _P, _I, _P, _P, _I, _P, _P, _P, _P, _I, _F, _F, _P, _P, _I, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P, _L)),
+    'a4r_lora_bwd_fused_ws_floats': (_I, (_I,)),
+    'a4r_phm_build': (_I, (_P, _P, _P, _I, _P)),
+    'a4r_phm_bwd': (_I, (_P, _P, _P, _I, _P)),
+    'a4r_unpack_add': (_I, (_P, _P, _P, _I, _I)),
+    'a4r_memset_zero': (_I, (_P, _P, _L)),
+    'a4r_eval_rank': (_I, (_P,) * 7 + (_I,) * 3),
+    'a4r_topk_ws_bytes': (_SZ, (_I, _I, _I)),
+    'a4r_topk_items': (_I, (_P,) * 8 + (_I,) * 4),
+    'a4r_score_ce_ws_bytes': (_SZ, (_I, _I, _I, _I)),
+    'a4r_score_ce_ranges': (_I, (_I, _I)),
+    'a4r_score_ce_fwd': (_I, (_P,) * 9 + (_I,) * 4),
+    'a4r_score_ce_bwd_rows': (_I, (_P,) * 7 + (_F, _P, _P, _P) + (_I,) * 4),
+    'a4r_score_ce_bwd_items': (_I, (_P,) * 7 + (_F, _P, _P) + (_I,) * 4),
+    'a4r_id_index': (_I, (_P, _P, _I, _I) + (_P,) * 7 + (_L,)),
+    'a4r_id_index_ws_ints': (_I, (_I, _I)),
+    'a4r_id_grad_sum': (_I, (_P, _P, _I, _P, _P, _P, _P, _I, _P, _I, _I)),
+    'a4r_id_sample': (_I, (_P, _P, _I, _I, _P, _I, _I, _U64, _U64, _I, _P, _P, _P)),
+    'a4r_encoder_layer_fwd': (_I, (_P, C.POINTER(EncoderLayer), _P, _P, _P)),
+    'a4r_encoder_layer_bwd': (_I, (_P, C.POINTER(EncoderLayer), _P, _P, _P, _P)),
+}
+EXPORTS = list(SIGNATURES)
+
+
 _lib = None
 
 
@@ -116,14 +193,13 @@ def lib():
                 f'{LIB_PATH} not found: build it with `python -c "import __graft_entry__ as g; g.build()"` '
                 '(hipcc --offload-arch=gfx950).  adapter4rec_amd has no CPU / PyTorch fallback.')
         _lib = C.CDLL(LIB_PATH)
-        missing = [name for name in EXPORTS if not hasattr(_lib, name)]
+        missing = [name for name in SIGNATURES if not hasattr(_lib, name)]
         if missing:                   # a build from before an entry point was added (additions keep the ABI number: no argument list changes)
             _lib = None
             raise RuntimeError(f'{LIB_PATH} lacks {", ".join(missing)}: rebuild it (make -C adapter4rec_amd/csrc)')
-        for name in EXPORTS:
-            getattr(_lib, name).restype = C.c_int
-        _lib.a4r_topk_ws_bytes.restype = C.c_size_t        # (the size_t-valued exports; not in EXPORTS, whose entries return a status)
-        _lib.a4r_score_ce_ws_bytes.restype = C.c_size_t
+        for name, (restype, argtypes) in SIGNATURES.items():
+            f = getattr(_lib, name)
+            f.restype, f.argtypes = restype, argtypes
         got = _lib.a4r_version()
         if got != ABI_VERSION:        # an older A/B build has every export but other argument lists: calling it would pass shifted pointers
             _lib = None
@@ -146,15 +222,11 @@ def _stream():
     global _DEV_INDEX
     if _DEV_INDEX is None:
         _DEV_INDEX = torch.cuda.current_device()
-    return C.c_void_p(torch._C._cuda_getCurrentRawStream(_DEV_INDEX))
+    return torch._C._cuda_getCurrentRawStream(_DEV_INDEX)
 
 
 def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-
-def _pi(t):
-    return t.data_ptr() if t is not None else 0
+    return t.data_ptr() if t is not None else None
 
 
 def _dt(t):
@@ -170,6 +242,10 @@ def _dt(t):
 def _ld(t):
     assert t.dim() == 2 and t.stride(1) == 1, 'row-major 2-D tensor expected'
     return t.stride(0)
+
+
+def _ld0(t):
+    return _ld(t) if t is not None else 0
 
 
 def require_gpu(*tensors):
@@ -199,32 +275,32 @@ def gemm_nt(A, B, Cout, bias=None, C2=None, R1=None, R2=None, Pre=None, act=0, d
     assert bias is None or bias.dtype == torch.float32
     # positional construction (field order of a4r_gemm_t): one C call instead of ~30 attribute stores -- this wrapper runs
     # ~220 times per training step
-    g = GemmArgs(A.data_ptr(), B.data_ptr(), Cout.data_ptr(), _pi(bias), _pi(C2), _pi(R1), _pi(R2), _pi(Pre),
+    g = GemmArgs(A.data_ptr(), B.data_ptr(), Cout.data_ptr(), _p(bias), _p(C2), _p(R1), _p(R2), _p(Pre),
                  A.shape[0] if M is None else M, N, K, _ld(A), _ld(B), _ld(Cout),
                  _ld(C2) if C2 is not None else 0, _ld(R1) if R1 is not None else 0, _ld(R2) if R2 is not None else 0,
                  _ld(Pre) if Pre is not None else 0, din, dout, act, dact, int(drop_first), 2 if q8c else int(bool(c2_deriv)), alpha, drop_p, drop_site,
-                 drop_seed, 0, _pi(scale_a), _pi(scale_b), int(c_fp8), float(c_scale), _pi(c_scale_out), int(bool(q8_tiled)))
+                 drop_seed, 0, _p(scale_a), _p(scale_b), int(c_fp8), float(c_scale), _p(c_scale_out), int(bool(q8_tiled)))
     _check(lib().a4r_gemm_nt(_stream(), C.byref(g)), 'a4r_gemm_nt')
 
 
 def gemm_variant(v):
-    return lib().a4r_gemm_variant(C.c_int(v))
+    return lib().a4r_gemm_variant(v)
 
 
 def gemm_tail_max(k):
-    return lib().a4r_gemm_tail_max(C.c_int(k))
+    return lib().a4r_gemm_tail_max(k)
 
 
 def gemm_tail_plan(M, N):
     """(p_full, kp): row panels of full 256-row tiles and the height / 32 of the short tiles behind them (kp = 0: none)."""
     pf, kp = C.c_int(0), C.c_int(0)
-    lib().a4r_gemm_tail_plan(C.c_int(M), C.c_int(N), C.byref(pf), C.byref(kp))
+    lib().a4r_gemm_tail_plan(M, N, C.byref(pf), C.byref(kp))
     return pf.value, kp.value
 
 
 def gemm_rows_256(M, N):
     """Leading rows of an [M, N] gemm_nt output that the 256-tile kernel computes (= the tile-native part of a q8_tiled tensor)."""
-    return lib().a4r_gemm_rows_256(C.c_int(M), C.c_int(N))
+    return lib().a4r_gemm_rows_256(M, N)
 
 
 def adapter_ln_ok(A, d):
@@ -246,14 +322,9 @@ def adapter_ln_fwd(A, R1, R2, Wd, bd, Wu, bu, gamma, beta, eps, act, zp, z, v, y
     lo4 = lo8 and twins[0].shape[1] == A.shape[1] // 2
     assert not lo8 or all(t.shape[1] == (A.shape[1] // 2 if lo4 else A.shape[1]) for t in twins)
     wd_, wu_ = (Wd, Wu) if frag is None else frag
-    _check(lib().a4r_adapter_ln_fwd(_stream(), _p(A), C.c_int(_ld(A)), _p(R1), C.c_int(_ld(R1)), _p(R2), C.c_int(_ld(R2) if R2 is not None else 0),
-                                    _p(wd_), _p(bd), _p(wu_), _p(bu), _p(gamma), _p(beta), C.c_float(eps), C.c_int(act),
-                                    _p(zp), _p(z), _p(v), C.c_int(_ld(v) if v is not None else 0), _p(y), C.c_int(_ld(y) if y is not None else 0), _p(stats),
-                                    C.c_int(M), C.c_int(A.shape[1]), C.c_int(Wd.shape[0]), C.c_int(_dt(A)),
-                                    _p(y8), C.c_int(_ld(y8) if y8 is not None else 0), _p(ys),
-                                    _p(res32), C.c_int(_ld(res32) if res32 is not None else 0), _p(y32), C.c_int(_ld(y32) if y32 is not None else 0),
-                                    C.c_int((0 if frag is None else 1) | (2 if lo8 else 0) | (4 if lo4 else 0))),
-           'a4r_adapter_ln_fwd')
+    _check(lib().a4r_adapter_ln_fwd(_stream(), _p(A), _ld(A), _p(R1), _ld(R1), _p(R2), _ld0(R2), _p(wd_), _p(bd), _p(wu_), _p(bu), _p(gamma), _p(beta), eps, act, _p(zp), _p(z),
+                                    _p(v), _ld0(v), _p(y), _ld0(y), _p(stats), M, A.shape[1], Wd.shape[0], _dt(A), _p(y8), _ld0(y8), _p(ys), _p(res32), _ld0(res32), _p(y32),
+                                    _ld0(y32), (0 if frag is None else 1) | (2 if lo8 else 0) | (4 if lo4 else 0)), 'a4r_adapter_ln_fwd')
 
 
 def adapter_ln_bwd(dy, v, stats, gamma, dres, zp, act, WuT, WdT, inner_res, dv, dzp, dh, dgamma=None, dbeta=None, dbias=None, M=None,
@@ -263,12 +334,9 @@ def adapter_ln_bwd(dy, v, stats, gamma, dres, zp, act, WuT, WdT, inner_res, dv, 
     require_gpu(dy, v, dv, dh)
     M = dy.shape[0] if M is None else M
     wut_, wdt_ = (WuT, WdT) if frag is None else frag
-    _check(lib().a4r_adapter_ln_bwd(_stream(), _p(dy), C.c_int(_ld(dy)), _p(v), C.c_int(_ld(v)), _p(stats), _p(gamma),
-                                    _p(dres), C.c_int(_ld(dres) if dres is not None else 0), _p(zp), C.c_int(act), _p(wut_), _p(wdt_),
-                                    C.c_int(int(inner_res)), _p(dv), C.c_int(_ld(dv)), _p(dzp), _p(dh), C.c_int(_ld(dh)),
-                                    _p(dgamma), _p(dbeta), _p(dbias), C.c_int(M), C.c_int(dy.shape[1]), C.c_int(WuT.shape[0]), C.c_int(_dt(dy)),
-                                    C.c_float(drop_p), C.c_uint32(drop_site), C.c_uint64(drop_seed), _p(dbd),
-                                    C.c_int(int(bias_total) | (0 if frag is None else 2)), _p(beta_y)), 'a4r_adapter_ln_bwd')
+    _check(lib().a4r_adapter_ln_bwd(_stream(), _p(dy), _ld(dy), _p(v), _ld(v), _p(stats), _p(gamma), _p(dres), _ld0(dres), _p(zp), act, _p(wut_), _p(wdt_), int(inner_res), _p(dv),
+                                    _ld(dv), _p(dzp), _p(dh), _ld(dh), _p(dgamma), _p(dbeta), _p(dbias), M, dy.shape[1], WuT.shape[0], _dt(dy), drop_p, drop_site, drop_seed,
+                                    _p(dbd), int(bias_total) | (0 if frag is None else 2), _p(beta_y)), 'a4r_adapter_ln_bwd')
 
 
 def sasrec_block(desc, x, log_mask, out, n_users, T, train, dy=None):
@@ -280,19 +348,17 @@ def sasrec_block(desc, x, log_mask, out, n_users, T, train, dy=None):
     for k, v in desc.items():
         setattr(b, k, (v.data_ptr() if v is not None else None) if (k in SasrecBlock._PTRS or k in ('ln3_g', 'ln3_b', 'g_ln3_g', 'g_ln3_b')) else v)
     if dy is None:
-        _check(lib().a4r_sasrec_block_fwd(_stream(), C.byref(b), _p(x), _p(log_mask), _p(out), C.c_int(n_users), C.c_int(T), C.c_int(int(train))), 'a4r_sasrec_block_fwd')
+        _check(lib().a4r_sasrec_block_fwd(_stream(), C.byref(b), _p(x), _p(log_mask), _p(out), n_users, T, int(train)), 'a4r_sasrec_block_fwd')
     else:
         assert dy.dtype == torch.float32 and dy.is_contiguous()
-        _check(lib().a4r_sasrec_block_bwd(_stream(), C.byref(b), _p(x), _p(log_mask), _p(dy), _p(out), C.c_int(n_users), C.c_int(T), C.c_int(int(train))),
-               'a4r_sasrec_block_bwd')
+        _check(lib().a4r_sasrec_block_bwd(_stream(), C.byref(b), _p(x), _p(log_mask), _p(dy), _p(out), n_users, T, int(train)), 'a4r_sasrec_block_bwd')
 
 
 def gemm_tn(X, Y, Cacc, M=None):
     require_gpu(X, Y, Cacc)
     assert Cacc.dtype == torch.float32 and _dt(X) == _dt(Y)
     M = X.shape[0] if M is None else M
-    _check(lib().a4r_gemm_tn(_stream(), _p(X), C.c_int(_ld(X)), _p(Y), C.c_int(_ld(Y)), _p(Cacc), C.c_int(_ld(Cacc)),
-                             C.c_int(M), C.c_int(X.shape[1]), C.c_int(Y.shape[1]), C.c_int(_dt(X))), 'a4r_gemm_tn')
+    _check(lib().a4r_gemm_tn(_stream(), _p(X), _ld(X), _p(Y), _ld(Y), _p(Cacc), _ld(Cacc), M, X.shape[1], Y.shape[1], _dt(X)), 'a4r_gemm_tn')
 
 
 def gemm_tn_bias(X, Y, Cacc, xsum, M=None):
@@ -300,13 +366,7 @@ def gemm_tn_bias(X, Y, Cacc, xsum, M=None):
     require_gpu(X, Y, Cacc, xsum)
     assert Cacc.dtype == torch.float32 and xsum.dtype == torch.float32 and xsum.numel() >= X.shape[1] and _dt(X) == _dt(Y)
     M = X.shape[0] if M is None else M
-    _check(lib().a4r_gemm_tn_bias(_stream(), _p(X), C.c_int(_ld(X)), _p(Y), C.c_int(_ld(Y)), _p(Cacc), C.c_int(_ld(Cacc)),
-                                  C.c_int(M), C.c_int(X.shape[1]), C.c_int(Y.shape[1]), C.c_int(_dt(X)), _p(xsum)), 'a4r_gemm_tn_bias')
-
-
-class TnProb(C.Structure):
-    _fields_ = [('X', C.c_void_p), ('Y', C.c_void_p), ('C', C.c_void_p), ('xsum', C.c_void_p),
-                ('ldx', C.c_int32), ('ldy', C.c_int32), ('ldc', C.c_int32), ('P', C.c_int32), ('Q', C.c_int32), ('pad_', C.c_int32)]
+    _check(lib().a4r_gemm_tn_bias(_stream(), _p(X), _ld(X), _p(Y), _ld(Y), _p(Cacc), _ld(Cacc), M, X.shape[1], Y.shape[1], _dt(X), _p(xsum)), 'a4r_gemm_tn_bias')
 
 
 def gemm_tn_multi(probs, M=None):
@@ -320,7 +380,7 @@ def gemm_tn_multi(probs, M=None):
         assert Cacc.dtype == torch.float32 and _dt(X) == dt and _dt(Y) == dt and (xsum is None or (xsum.dtype == torch.float32 and xsum.numel() >= X.shape[1]))
         a.X, a.Y, a.C, a.xsum = X.data_ptr(), Y.data_ptr(), Cacc.data_ptr(), (xsum.data_ptr() if xsum is not None else None)
         a.ldx, a.ldy, a.ldc, a.P, a.Q = _ld(X), _ld(Y), _ld(Cacc), X.shape[1], Y.shape[1]
-    _check(lib().a4r_gemm_tn_multi(_stream(), arr, C.c_int(len(probs)), C.c_int(M), C.c_int(dt)), 'a4r_gemm_tn_multi')
+    _check(lib().a4r_gemm_tn_multi(_stream(), arr, len(probs), M, dt), 'a4r_gemm_tn_multi')
 
 
 def gemm_tn2(X1, Y1, C1, X2, Y2, C2, M=None, xsum1=None, xsum2=None):
@@ -329,15 +389,14 @@ def gemm_tn2(X1, Y1, C1, X2, Y2, C2, M=None, xsum1=None, xsum2=None):
     assert C1.dtype == torch.float32 and C2.dtype == torch.float32
     assert (xsum1 is None or (xsum1.dtype == torch.float32 and xsum1.numel() >= X1.shape[1])) and (xsum2 is None or (xsum2.dtype == torch.float32 and xsum2.numel() >= X2.shape[1]))
     M = X1.shape[0] if M is None else M
-    _check(lib().a4r_gemm_tn2(_stream(), _p(X1), C.c_int(_ld(X1)), _p(Y1), C.c_int(_ld(Y1)), _p(C1), C.c_int(_ld(C1)), C.c_int(X1.shape[1]), C.c_int(Y1.shape[1]),
-                              _p(X2), C.c_int(_ld(X2)), _p(Y2), C.c_int(_ld(Y2)), _p(C2), C.c_int(_ld(C2)), C.c_int(X2.shape[1]), C.c_int(Y2.shape[1]),
-                              C.c_int(M), C.c_int(_dt(X1)), _p(xsum1), _p(xsum2)), 'a4r_gemm_tn2')
+    _check(lib().a4r_gemm_tn2(_stream(), _p(X1), _ld(X1), _p(Y1), _ld(Y1), _p(C1), _ld(C1), X1.shape[1], Y1.shape[1], _p(X2), _ld(X2), _p(Y2), _ld(Y2), _p(C2), _ld(C2),
+                              X2.shape[1], Y2.shape[1], M, _dt(X1), _p(xsum1), _p(xsum2)), 'a4r_gemm_tn2')
 
 
 def colsum(X, out, M=None):
     require_gpu(X, out)
     M = X.shape[0] if M is None else M
-    _check(lib().a4r_colsum(_stream(), _p(X), C.c_int(_ld(X)), _p(out), C.c_int(M), C.c_int(X.shape[1]), C.c_int(_dt(X))), 'a4r_colsum')
+    _check(lib().a4r_colsum(_stream(), _p(X), _ld(X), _p(out), M, X.shape[1], _dt(X)), 'a4r_colsum')
 
 
 def _attn_args(qkv, q_off, k_off, v_off, key_mask, n_items, S, n_heads, dh, causal, scale, mask_neg, drop_p, drop_site, drop_seed, offsets=None):
@@ -415,8 +474,7 @@ def patchify(img, out, patch, keep_idx=None):
         kind, (n, Cc, Hi, Wi) = 0, img.shape
     n_keep = keep_idx.shape[1] if keep_idx is not None else (Hi // patch) * (Wi // patch)
     assert keep_idx is None or (keep_idx.dtype == torch.int32 and keep_idx.is_contiguous() and keep_idx.shape[0] == n)
-    _check(lib().a4r_patchify(_stream(), _p(img), C.c_int(kind), _p(out), C.c_int(_ld(out)), _p(keep_idx), C.c_int(n_keep),
-                              C.c_int(n), C.c_int(Cc), C.c_int(Hi), C.c_int(Wi), C.c_int(patch), C.c_int(_dt(out))), 'a4r_patchify')
+    _check(lib().a4r_patchify(_stream(), _p(img), kind, _p(out), _ld(out), _p(keep_idx), n_keep, n, Cc, Hi, Wi, patch, _dt(out)), 'a4r_patchify')
 
 
 def mae_keep_indices(keep, n_patches, noise=None, seed=0, site=0):
@@ -424,23 +482,20 @@ def mae_keep_indices(keep, n_patches, noise=None, seed=0, site=0):
     require_gpu(keep, noise)
     assert keep.dtype == torch.int32 and keep.is_contiguous()
     assert noise is None or (noise.dtype == torch.float32 and noise.is_contiguous() and tuple(noise.shape) == (keep.shape[0], n_patches))
-    _check(lib().a4r_mae_keep_indices(_stream(), _p(noise), _p(keep), C.c_int(keep.shape[0]), C.c_int(n_patches), C.c_int(keep.shape[1]),
-                                      C.c_uint64(int(seed) & (2 ** 64 - 1)), C.c_uint32(site)), 'a4r_mae_keep_indices')
+    _check(lib().a4r_mae_keep_indices(_stream(), _p(noise), _p(keep), keep.shape[0], n_patches, keep.shape[1], int(seed) & (2 ** 64 - 1), site), 'a4r_mae_keep_indices')
 
 
 def resample_u8(src, dst, bounds, kk, n_outer, in_len, out_len, inner):
     require_gpu(src, dst, bounds, kk)
     assert src.dtype == torch.uint8 and dst.dtype == torch.uint8 and bounds.dtype == torch.int32 and kk.dtype == torch.int32
     assert src.is_contiguous() and dst.is_contiguous() and src.numel() == n_outer * in_len * inner and dst.numel() == n_outer * out_len * inner
-    _check(lib().a4r_resample_u8(_stream(), _p(src), _p(dst), _p(bounds), _p(kk), C.c_int(kk.shape[1]), C.c_long(n_outer),
-                                 C.c_int(in_len), C.c_int(out_len), C.c_long(inner)), 'a4r_resample_u8')
+    _check(lib().a4r_resample_u8(_stream(), _p(src), _p(dst), _p(bounds), _p(kk), kk.shape[1], n_outer, in_len, out_len, inner), 'a4r_resample_u8')
 
 
 def vit_assemble(patches, cls, pos, out, n_items, n_keep, keep_idx=None, tokens_out=0):
     require_gpu(patches, out)
-    _check(lib().a4r_vit_assemble(_stream(), _p(patches), C.c_int(_ld(patches)), _p(cls), _p(pos), _p(keep_idx), _p(out),
-                                  C.c_int(_ld(out)), C.c_int(n_items), C.c_int(n_keep), C.c_int(cls.numel()), C.c_int(_dt(out)),
-                                  C.c_int(tokens_out)), 'a4r_vit_assemble')
+    _check(lib().a4r_vit_assemble(_stream(), _p(patches), _ld(patches), _p(cls), _p(pos), _p(keep_idx), _p(out), _ld(out), n_items, n_keep, cls.numel(), _dt(out), tokens_out),
+           'a4r_vit_assemble')
 
 
 def embed_bwd(ids, dpre, dword, dpos, n_items, S, roberta=False, pad_id=0):
@@ -457,19 +512,16 @@ def embed_bwd(ids, dpre, dword, dpos, n_items, S, roberta=False, pad_id=0):
     n_pos = S + pad_id + 1 if roberta else S         # largest pos_id + 1 (RoBERTa: cumsum(id != pad) + pad <= S + pad)
     assert dpos is None or dpos.shape[0] >= n_pos, f'dpos has {dpos.shape[0]} rows, position ids reach {n_pos - 1}'
     require_gpu(ids, dpre, dword, dpos)
-    _check(lib().a4r_embed_bwd(_stream(), _p(ids), C.c_int(ids.stride(0)), _p(dpre), C.c_int(_ld(dpre)), _p(dword), _p(dpos),
-                               C.c_int(n_items), C.c_int(S), C.c_int(dpre.shape[1]), C.c_int(int(roberta)), C.c_int(pad_id),
-                               C.c_int(_dt(dpre))), 'a4r_embed_bwd')
+    _check(lib().a4r_embed_bwd(_stream(), _p(ids), ids.stride(0), _p(dpre), _ld(dpre), _p(dword), _p(dpos), n_items, S, dpre.shape[1], int(roberta), pad_id, _dt(dpre)),
+           'a4r_embed_bwd')
 
 
 def embed_ln(ids, word, pos, type0, gamma, beta, eps, out, n_items, S, roberta=False, pad_id=0,
              drop_p=0.0, drop_site=0, drop_seed=0, pre_out=None, stats_out=None, key_mask_out=None):
     require_gpu(ids, word, out)
     assert ids.dtype == torch.int64 and ids.stride(1) == 1
-    _check(lib().a4r_embed_ln(_stream(), _p(ids), C.c_int(ids.stride(0)), _p(word), _p(pos), _p(type0), _p(gamma), _p(beta),
-                              C.c_float(eps), _p(out), C.c_int(_ld(out)), C.c_int(n_items), C.c_int(S), C.c_int(word.shape[1]),
-                              C.c_int(int(roberta)), C.c_int(pad_id), C.c_int(_dt(out)),
-                              C.c_float(drop_p), C.c_uint32(drop_site), C.c_uint64(drop_seed), _p(pre_out), _p(stats_out), _p(key_mask_out)), 'a4r_embed_ln')
+    _check(lib().a4r_embed_ln(_stream(), _p(ids), ids.stride(0), _p(word), _p(pos), _p(type0), _p(gamma), _p(beta), eps, _p(out), _ld(out), n_items, S, word.shape[1], int(roberta),
+                              pad_id, _dt(out), drop_p, drop_site, drop_seed, _p(pre_out), _p(stats_out), _p(key_mask_out)), 'a4r_embed_ln')
 
 
 def quantize_weight_fp8(w):
@@ -485,8 +537,7 @@ def quant_rows_fp8(x, q, scale, M=None):
     require_gpu(x, q, scale)
     M = x.shape[0] if M is None else M
     assert q.dtype == torch.uint8 and scale.dtype == torch.float32
-    _check(lib().a4r_quant_rows_fp8(_stream(), _p(x), C.c_int(_ld(x)), _p(q), C.c_int(_ld(q)), _p(scale), C.c_int(M), C.c_int(x.shape[1]),
-                                    C.c_int(_dt(x))), 'a4r_quant_rows_fp8')
+    _check(lib().a4r_quant_rows_fp8(_stream(), _p(x), _ld(x), _p(q), _ld(q), _p(scale), M, x.shape[1], _dt(x)), 'a4r_quant_rows_fp8')
 
 
 def ln_fwd_sum(h, res, gamma, beta, eps, y, stats, M=None, res32=None, sum_out=None, sum32=None, y32=None):
@@ -495,11 +546,8 @@ def ln_fwd_sum(h, res, gamma, beta, eps, y, stats, M=None, res32=None, sum_out=N
     require_gpu(h, res, res32, y, sum_out, sum32, y32)
     M = h.shape[0] if M is None else M
     assert res32 is not None or res is not None
-    _check(lib().a4r_ln_fwd_sum(_stream(), _p(h), C.c_int(_ld(h)), _p(res32), C.c_int(_ld(res32) if res32 is not None else 0), _p(res),
-                                C.c_int(_ld(res) if res is not None else 0), _p(gamma), _p(beta), C.c_float(eps), _p(y), C.c_int(_ld(y)),
-                                _p(sum_out), C.c_int(_ld(sum_out) if sum_out is not None else 0), _p(sum32), C.c_int(_ld(sum32) if sum32 is not None else 0),
-                                _p(y32), C.c_int(_ld(y32) if y32 is not None else 0), _p(stats), C.c_int(M), C.c_int(h.shape[1]), C.c_int(_dt(h))),
-           'a4r_ln_fwd_sum')
+    _check(lib().a4r_ln_fwd_sum(_stream(), _p(h), _ld(h), _p(res32), _ld0(res32), _p(res), _ld0(res), _p(gamma), _p(beta), eps, _p(y), _ld(y), _p(sum_out), _ld0(sum_out),
+                                _p(sum32), _ld0(sum32), _p(y32), _ld0(y32), _p(stats), M, h.shape[1], _dt(h)), 'a4r_ln_fwd_sum')
 
 
 def ln_fwd(v, gamma, beta, eps, y, stats, M=None, add=None, drop_p=0.0, drop_site=0, drop_seed=0, y8=None, ys=None):
@@ -507,31 +555,25 @@ def ln_fwd(v, gamma, beta, eps, y, stats, M=None, add=None, drop_p=0.0, drop_sit
     M = v.shape[0] if M is None else M
     if y8 is not None:                    # also emit the row as e4m3 + per-row scale (y may be None)
         assert drop_p == 0.0 and y8.dtype == torch.uint8 and ys.dtype == torch.float32
-        _check(lib().a4r_ln_fwd_fp8(_stream(), _p(v), C.c_int(_ld(v)), _p(add), C.c_int(add.shape[0] if add is not None else 0),
-                                    _p(gamma), _p(beta), C.c_float(eps), _p(y), C.c_int(_ld(y) if y is not None else 0), _p(y8), C.c_int(_ld(y8)),
-                                    _p(ys), _p(stats), C.c_int(M), C.c_int(v.shape[1]), C.c_int(_dt(v))), 'a4r_ln_fwd_fp8')
+        _check(lib().a4r_ln_fwd_fp8(_stream(), _p(v), _ld(v), _p(add), add.shape[0] if add is not None else 0, _p(gamma), _p(beta), eps, _p(y), _ld0(y), _p(y8), _ld(y8), _p(ys),
+                                    _p(stats), M, v.shape[1], _dt(v)), 'a4r_ln_fwd_fp8')
         return
-    _check(lib().a4r_ln_fwd(_stream(), _p(v), C.c_int(_ld(v)), _p(add), C.c_int(add.shape[0] if add is not None else 0),
-                            _p(gamma), _p(beta), C.c_float(eps), _p(y), C.c_int(_ld(y)), _p(stats), C.c_int(M),
-                            C.c_int(v.shape[1]), C.c_int(_dt(v)), C.c_float(drop_p), C.c_uint32(drop_site), C.c_uint64(drop_seed)),
-           'a4r_ln_fwd')
+    _check(lib().a4r_ln_fwd(_stream(), _p(v), _ld(v), _p(add), add.shape[0] if add is not None else 0, _p(gamma), _p(beta), eps, _p(y), _ld(y), _p(stats), M, v.shape[1], _dt(v),
+                            drop_p, drop_site, drop_seed), 'a4r_ln_fwd')
 
 
 def ln_bwd(dy, v, stats, gamma, dv, M=None, add=None, dgamma=None, dbeta=None, dbias=None, dres=None,
            drop_p=0.0, drop_site=0, drop_seed=0, dv2=None, drop2_p=0.0, drop2_site=0, drop2_seed=0):
     require_gpu(dy, v, dv)
     M = v.shape[0] if M is None else M
-    _check(lib().a4r_ln_bwd(_stream(), _p(dy), C.c_int(_ld(dy)), _p(v), C.c_int(_ld(v)), _p(add),
-                            C.c_int(add.shape[0] if add is not None else 0), _p(stats), _p(gamma), _p(dres), C.c_int(_ld(dres) if dres is not None else 0), _p(dv), C.c_int(_ld(dv)),
-                            _p(dgamma), _p(dbeta), _p(dbias), C.c_int(M), C.c_int(v.shape[1]), C.c_int(_dt(v)),
-                            C.c_float(drop_p), C.c_uint32(drop_site), C.c_uint64(drop_seed),
-                            _p(dv2), C.c_int(_ld(dv2) if dv2 is not None else 0), C.c_float(drop2_p), C.c_uint32(drop2_site), C.c_uint64(drop2_seed)), 'a4r_ln_bwd')
+    _check(lib().a4r_ln_bwd(_stream(), _p(dy), _ld(dy), _p(v), _ld(v), _p(add), add.shape[0] if add is not None else 0, _p(stats), _p(gamma), _p(dres), _ld0(dres), _p(dv), _ld(dv),
+                            _p(dgamma), _p(dbeta), _p(dbias), M, v.shape[1], _dt(v), drop_p, drop_site, drop_seed, _p(dv2), _ld0(dv2), drop2_p, drop2_site, drop2_seed),
+           'a4r_ln_bwd')
 
 
 def gather_rows(src, dst, n, row_step):
     require_gpu(src, dst)
-    _check(lib().a4r_gather_rows(_stream(), _p(src), C.c_int(_ld(src)), _p(dst), C.c_int(_ld(dst)), C.c_int(n), C.c_int(row_step),
-                                 C.c_int(src.shape[1]), C.c_int(_dt(src))), 'a4r_gather_rows')
+    _check(lib().a4r_gather_rows(_stream(), _p(src), _ld(src), _p(dst), _ld(dst), n, row_step, src.shape[1], _dt(src)), 'a4r_gather_rows')
 
 
 def rows_idx_copy(src, dst, idx, n, scatter=False):
@@ -539,13 +581,12 @@ def rows_idx_copy(src, dst, idx, n, scatter=False):
     require_gpu(src, dst, idx)
     assert src.dim() == 2 and dst.dim() == 2 and src.dtype == dst.dtype and src.shape[1] == dst.shape[1] and idx.dtype == torch.int32 and idx.numel() >= n
     es = src.element_size()
-    _check(lib().a4r_rows_idx_copy(_stream(), _p(src), C.c_int64(src.stride(0) * es), _p(dst), C.c_int64(dst.stride(0) * es), _p(idx), C.c_int(n),
-                                   C.c_int64(src.shape[1] * es), C.c_int(int(scatter))), 'a4r_rows_idx_copy')
+    _check(lib().a4r_rows_idx_copy(_stream(), _p(src), src.stride(0) * es, _p(dst), dst.stride(0) * es, _p(idx), n, src.shape[1] * es, int(scatter)), 'a4r_rows_idx_copy')
 
 
 def id_index_ws_ints(n, item_num):
     """int32 elements of a4r_id_index's workspace (a host-side query, no GPU)."""
-    k = int(lib().a4r_id_index_ws_ints(C.c_int(n), C.c_int(item_num)))
+    k = int(lib().a4r_id_index_ws_ints(n, item_num))
     if k < 0:
         raise RuntimeError(f'a4r_id_index: n = {n}, item_num = {item_num} outside the supported range (include/a4r.h)')
     return k
@@ -558,36 +599,32 @@ def id_index(ids, item_num, rows, slots, ptr, uniq, n_uniq, err, ws):
     assert ids.dtype == torch.int64 and ids.is_contiguous() and ws.dtype == torch.int32
     assert all(t.dtype == torch.int32 for t in (rows, slots, ptr, uniq, n_uniq, err))
     assert rows.numel() >= n and slots.numel() >= n and ptr.numel() >= n + 1 and uniq.numel() >= n
-    _check(lib().a4r_id_index(_stream(), _p(ids), C.c_int(n), C.c_int(item_num), _p(rows), _p(slots), _p(ptr), _p(uniq), _p(n_uniq), _p(err),
-                              _p(ws), C.c_int64(ws.numel())), 'a4r_id_index')
+    _check(lib().a4r_id_index(_stream(), _p(ids), n, item_num, _p(rows), _p(slots), _p(ptr), _p(uniq), _p(n_uniq), _p(err), _p(ws), ws.numel()), 'a4r_id_index')
 
 
 def id_grad_sum(src, slots, ptr, uniq, n_uniq, n, grad):
     """grad[uniq[u]] += the ordered chunked sum of src[slots[ptr[u] .. ptr[u + 1])] for u < *n_uniq (a4r_id_grad_sum); src, grad fp32 2-D."""
     require_gpu(src, slots, ptr, uniq, n_uniq, grad)
     assert src.dtype == torch.float32 and grad.dtype == torch.float32 and src.shape[1] == grad.shape[1] and src.shape[0] >= n
-    _check(lib().a4r_id_grad_sum(_stream(), _p(src), C.c_int(_ld(src)), _p(slots), _p(ptr), _p(uniq), _p(n_uniq), C.c_int(n), _p(grad),
-                                 C.c_int(_ld(grad)), C.c_int(grad.shape[1])), 'a4r_id_grad_sum')
+    _check(lib().a4r_id_grad_sum(_stream(), _p(src), _ld(src), _p(slots), _p(ptr), _p(uniq), _p(n_uniq), n, _p(grad), _ld(grad), grad.shape[1]), 'a4r_id_grad_sum')
 
 
 def scatter_rows(src, dst, n, row_step):
     require_gpu(src, dst)
-    _check(lib().a4r_scatter_rows(_stream(), _p(src), C.c_int(_ld(src)), _p(dst), C.c_int(_ld(dst)), C.c_int(n), C.c_int(row_step),
-                                  C.c_int(src.shape[1]), C.c_int(_dt(src))), 'a4r_scatter_rows')
+    _check(lib().a4r_scatter_rows(_stream(), _p(src), _ld(src), _p(dst), _ld(dst), n, row_step, src.shape[1], _dt(src)), 'a4r_scatter_rows')
 
 
 def scatter_rows_fill(src, dst, n, row_step, fill_rows):
     """dst[r] = src[r / row_step] for r % row_step == 0 (r / row_step < n), 0 elsewhere, r < fill_rows."""
     require_gpu(src, dst)
-    _check(lib().a4r_scatter_rows_fill(_stream(), _p(src), C.c_int(_ld(src)), _p(dst), C.c_int(_ld(dst)), C.c_int(n), C.c_int(row_step),
-                                       C.c_int(src.shape[1]), C.c_int(_dt(src)), C.c_int(fill_rows)), 'a4r_scatter_rows_fill')
+    _check(lib().a4r_scatter_rows_fill(_stream(), _p(src), _ld(src), _p(dst), _ld(dst), n, row_step, src.shape[1], _dt(src), fill_rows), 'a4r_scatter_rows_fill')
 
 
 def zero(t):
     """hipMemsetAsync of a contiguous tensor on the current stream."""
     require_gpu(t)
     assert t.is_contiguous()
-    _check(lib().a4r_memset_zero(_stream(), _p(t), C.c_int64(t.numel() * t.element_size())), 'a4r_memset_zero')
+    _check(lib().a4r_memset_zero(_stream(), _p(t), t.numel() * t.element_size()), 'a4r_memset_zero')
 
 
 def lora_merge(W, A, B, scaling, dst, dstT, r):
@@ -595,14 +632,8 @@ def lora_merge(W, A, B, scaling, dst, dstT, r):
     require_gpu(W, dst, dstT)
     out_f, in_f = W.shape
     assert W.dtype == torch.float32 and W.is_contiguous() and (r == 0 or (A.is_contiguous() and B.is_contiguous()))
-    _check(lib().a4r_lora_merge(_stream(), _p(W), _p(A) if r else C.c_void_p(0), _p(B) if r else C.c_void_p(0), C.c_float(scaling),
-                                _p(dst), C.c_int(_ld(dst)), _p(dstT), C.c_int(_ld(dstT)), C.c_int(out_f), C.c_int(in_f), C.c_int(r),
-                                C.c_int(_dt(dst))), 'a4r_lora_merge')
-
-
-class LoraDesc(C.Structure):
-    _fields_ = [('W', C.c_void_p), ('A', C.c_void_p), ('B', C.c_void_p), ('dst', C.c_void_p), ('dstT', C.c_void_p),
-                ('scaling', C.c_float), ('ld', C.c_int32), ('ldT', C.c_int32), ('out_f', C.c_int32), ('in_f', C.c_int32), ('r', C.c_int32)]
+    _check(lib().a4r_lora_merge(_stream(), _p(W), _p(A) if r else None, _p(B) if r else None, scaling, _p(dst), _ld(dst), _p(dstT), _ld(dstT), out_f, in_f, r, _dt(dst)),
+           'a4r_lora_merge')
 
 
 def lora_table(entries, device):
@@ -617,7 +648,7 @@ def lora_table(entries, device):
 
 def lora_merge_batch(tab):
     t, n, mx, code = tab
-    _check(lib().a4r_lora_merge_batch(_stream(), _p(t), C.c_int(n), C.c_int(mx), C.c_int(code)), 'a4r_lora_merge_batch')
+    _check(lib().a4r_lora_merge_batch(_stream(), _p(t), n, mx, code), 'a4r_lora_merge_batch')
 
 
 def lora_bwd_fused_ok(x, M, H):
@@ -642,11 +673,9 @@ def lora_bwd_fused(x, dqa, dqb, Aa, Ab, BTa, BTb, scale_a, scale_b, dAa, dAb, dB
             ldbias = bvec.stride(0)
     ws = _lora_ws.get(x.device)                      # the workgroups' column sums before their reduction: one buffer per device (stream-ordered reuse)
     if ws is None:
-        ws = _lora_ws[x.device] = torch.empty(int(lib().a4r_lora_bwd_fused_ws_floats(C.c_int(H))), dtype=torch.float32, device=x.device)
-    _check(lib().a4r_lora_bwd_fused(_stream(), _p(x), C.c_int(_ld(x)), _p(dqa), _p(dqb), C.c_int(_ld(dqa)), _p(Aa), _p(Ab), _p(BTa), _p(BTb),
-                                    C.c_int(_ld(Aa)), C.c_float(scale_a), C.c_float(scale_b), _p(dAa), _p(dAb), C.c_int(_ld(dAa)), _p(dBa), _p(dBb),
-                                    C.c_int(_ld(dBa)), _p(dbias_a), _p(dbias_b), C.c_int(ldbias), C.c_int(M), C.c_int(H), C.c_int(_dt(x)),
-                                    C.c_int(rank_rows), _p(ws), C.c_int64(ws.numel())), 'a4r_lora_bwd_fused')
+        ws = _lora_ws[x.device] = torch.empty(int(lib().a4r_lora_bwd_fused_ws_floats(H)), dtype=torch.float32, device=x.device)
+    _check(lib().a4r_lora_bwd_fused(_stream(), _p(x), _ld(x), _p(dqa), _p(dqb), _ld(dqa), _p(Aa), _p(Ab), _p(BTa), _p(BTb), _ld(Aa), scale_a, scale_b, _p(dAa), _p(dAb), _ld(dAa),
+                                    _p(dBa), _p(dBb), _ld(dBa), _p(dbias_a), _p(dbias_b), ldbias, M, H, _dt(x), rank_rows, _p(ws), ws.numel()), 'a4r_lora_bwd_fused')
 
 
 def desc_table(entries, device):
@@ -656,46 +685,44 @@ def desc_table(entries, device):
 
 
 def phm_build(params, desc_dev, n_desc, eff):
-    _check(lib().a4r_phm_build(_stream(), _p(params), _p(desc_dev), C.c_int(n_desc), _p(eff)), 'a4r_phm_build')
+    _check(lib().a4r_phm_build(_stream(), _p(params), _p(desc_dev), n_desc, _p(eff)), 'a4r_phm_build')
 
 
 def phm_bwd(params, desc_dev, n_desc, grads):
-    _check(lib().a4r_phm_bwd(_stream(), _p(params), _p(desc_dev), C.c_int(n_desc), _p(grads)), 'a4r_phm_bwd')
+    _check(lib().a4r_phm_bwd(_stream(), _p(params), _p(desc_dev), n_desc, _p(grads)), 'a4r_phm_bwd')
 
 
 def unpack_add(target, desc_dev, n_desc, max_elems):
-    _check(lib().a4r_unpack_add(_stream(), _p(target), _p(desc_dev), C.c_int(n_desc), C.c_int(max_elems)), 'a4r_unpack_add')
+    _check(lib().a4r_unpack_add(_stream(), _p(target), _p(desc_dev), n_desc, max_elems), 'a4r_unpack_add')
 
 
 def dropout_apply(x, y, drop_p, drop_site, drop_seed, M=None):
     require_gpu(x, y)
     M = x.shape[0] if M is None else M
-    _check(lib().a4r_dropout_apply(_stream(), _p(x), C.c_int(_ld(x)), _p(y), C.c_int(_ld(y)), C.c_int(M), C.c_int(x.shape[1]),
-                                   C.c_int(_dt(x)), C.c_float(drop_p), C.c_uint32(drop_site), C.c_uint64(drop_seed)), 'a4r_dropout_apply')
+    _check(lib().a4r_dropout_apply(_stream(), _p(x), _ld(x), _p(y), _ld(y), M, x.shape[1], _dt(x), drop_p, drop_site, drop_seed), 'a4r_dropout_apply')
 
 
 def act_bwd_f32(dy, pre, dx, act):
     require_gpu(dy, pre, dx)
-    _check(lib().a4r_act_bwd_f32(_stream(), _p(dy), _p(pre), _p(dx), C.c_int64(dy.numel()), C.c_int(act)), 'a4r_act_bwd_f32')
+    _check(lib().a4r_act_bwd_f32(_stream(), _p(dy), _p(pre), _p(dx), dy.numel(), act), 'a4r_act_bwd_f32')
 
 
 def score_bce_fwd(emb, prec, log_mask, pos, neg, loss_ws, B, L, E, cpc):
     require_gpu(emb, prec)
-    _check(lib().a4r_score_bce_fwd(_stream(), _p(emb), _p(prec), _p(log_mask), _p(pos), _p(neg), _p(loss_ws),
-                                   C.c_int(B), C.c_int(L), C.c_int(E), C.c_int(int(cpc))), 'a4r_score_bce_fwd')
+    _check(lib().a4r_score_bce_fwd(_stream(), _p(emb), _p(prec), _p(log_mask), _p(pos), _p(neg), _p(loss_ws), B, L, E, int(cpc)), 'a4r_score_bce_fwd')
 
 
 def score_bce_bwd(emb, prec, log_mask, pos, neg, loss_ws, loss_scale, d_prec, d_emb, B, L, E, cpc, scale_dev=None):
     require_gpu(emb, prec, scale_dev)
     assert scale_dev is None or (scale_dev.dtype == torch.float32 and scale_dev.numel() == 1)
-    _check(lib().a4r_score_bce_bwd(_stream(), _p(emb), _p(prec), _p(log_mask), _p(pos), _p(neg), _p(loss_ws), C.c_float(loss_scale), _p(scale_dev),
-                                   _p(d_prec), _p(d_emb), C.c_int(B), C.c_int(L), C.c_int(E), C.c_int(int(cpc))), 'a4r_score_bce_bwd')
+    _check(lib().a4r_score_bce_bwd(_stream(), _p(emb), _p(prec), _p(log_mask), _p(pos), _p(neg), _p(loss_ws), loss_scale, _p(scale_dev), _p(d_prec), _p(d_emb), B, L, E, int(cpc)),
+           'a4r_score_bce_bwd')
 
 
 def score_ce_ranges(R, N1):
     """The library's own item-range count for R rows against an [N1, E] table (a host-side query): <= SCORE_CE_MAX_RANGES and <= the table's
     16-item tiles."""
-    k = int(lib().a4r_score_ce_ranges(C.c_int(R), C.c_int(N1)))
+    k = int(lib().a4r_score_ce_ranges(R, N1))
     if k < 1:
         raise ValueError(f'score_ce_ranges: R = {R} rows and N1 = {N1} table rows (row 0 = the pad item): need R >= 1, N1 >= 2')
     return k
@@ -704,7 +731,7 @@ def score_ce_ranges(R, N1):
 def score_ce_ws_bytes(R, N1, E, ranges=0):
     """Bytes of the workspace a4r_score_ce_fwd / _bwd_rows share (a host-side query); ranges 0 = the library's choice.  0 for arguments the
     kernels refuse.  Independent of N1 at a fixed range count: nothing of size rows x items exists."""
-    return int(lib().a4r_score_ce_ws_bytes(C.c_int(R), C.c_int(N1), C.c_int(E), C.c_int(ranges)))
+    return int(lib().a4r_score_ce_ws_bytes(R, N1, E, ranges))
 
 
 def _score_ce_ws(prec, R, N1, E, ranges, ws):
@@ -732,8 +759,7 @@ def score_ce_fwd(prec, table, tgt, log_mask, lse, s_tgt, loss_ws, R, ranges=0, w
     assert all(t.dtype == torch.float32 and t.is_contiguous() for t in (lse, s_tgt, loss_ws)) and lse.numel() >= R and s_tgt.numel() >= R and loss_ws.numel() >= 4
     N1, E = table.shape
     ws = _score_ce_ws(prec, R, N1, E, ranges, ws)
-    _check(lib().a4r_score_ce_fwd(_stream(), _p(prec), _p(table), _p(tgt), _p(log_mask), _p(lse), _p(s_tgt), _p(loss_ws), _p(ws),
-                                  C.c_int(R), C.c_int(N1), C.c_int(E), C.c_int(ranges)), 'a4r_score_ce_fwd')
+    _check(lib().a4r_score_ce_fwd(_stream(), _p(prec), _p(table), _p(tgt), _p(log_mask), _p(lse), _p(s_tgt), _p(loss_ws), _p(ws), R, N1, E, ranges), 'a4r_score_ce_fwd')
 
 
 def score_ce_bwd(prec, table, tgt, log_mask, lse, loss_ws, loss_scale, d_prec, d_table, R, ranges=0, scale_dev=None, ws=None):
@@ -747,30 +773,26 @@ def score_ce_bwd(prec, table, tgt, log_mask, lse, loss_ws, loss_scale, d_prec, d
     if d_prec is not None:
         assert d_prec.dtype == torch.float32 and d_prec.is_contiguous() and d_prec.shape[1] == E and d_prec.shape[0] >= R
         ws = _score_ce_ws(prec, R, N1, E, ranges, ws)
-        _check(lib().a4r_score_ce_bwd_rows(_stream(), _p(prec), _p(table), _p(tgt), _p(log_mask), _p(lse), _p(loss_ws), C.c_float(loss_scale),
-                                           _p(scale_dev), _p(d_prec), _p(ws), C.c_int(R), C.c_int(N1), C.c_int(E), C.c_int(ranges)),
-               'a4r_score_ce_bwd_rows')
+        _check(lib().a4r_score_ce_bwd_rows(_stream(), _p(prec), _p(table), _p(tgt), _p(log_mask), _p(lse), _p(loss_ws), loss_scale, _p(scale_dev), _p(d_prec), _p(ws), R, N1, E,
+                                           ranges), 'a4r_score_ce_bwd_rows')
     if d_table is not None:
         assert d_table.dtype == torch.float32 and d_table.dim() == 2 and d_table.stride(1) == 1 and d_table.shape[0] >= N1
-        _check(lib().a4r_score_ce_bwd_items(_stream(), _p(prec), _p(table), _p(tgt), _p(log_mask), _p(lse), _p(loss_ws), C.c_float(loss_scale),
-                                            _p(scale_dev), _p(d_table), C.c_int(d_table.stride(0)), C.c_int(R), C.c_int(N1), C.c_int(E)),
-               'a4r_score_ce_bwd_items')
+        _check(lib().a4r_score_ce_bwd_items(_stream(), _p(prec), _p(table), _p(tgt), _p(log_mask), _p(lse), _p(loss_ws), loss_scale, _p(scale_dev), _p(d_table), d_table.stride(0),
+                                            R, N1, E), 'a4r_score_ce_bwd_items')
 
 
 def emb_grad_add_inputs(d_in, d_emb, B, L, E):
-    _check(lib().a4r_emb_grad_add_inputs(_stream(), _p(d_in), C.c_int(_ld(d_in)), _p(d_emb), C.c_int(B), C.c_int(L), C.c_int(E)),
-           'a4r_emb_grad_add_inputs')
+    _check(lib().a4r_emb_grad_add_inputs(_stream(), _p(d_in), _ld(d_in), _p(d_emb), B, L, E), 'a4r_emb_grad_add_inputs')
 
 
 def take_inputs(emb, out, B, L, E):
-    _check(lib().a4r_take_inputs(_stream(), _p(emb), _p(out), C.c_int(_ld(out)), C.c_int(B), C.c_int(L), C.c_int(E)), 'a4r_take_inputs')
+    _check(lib().a4r_take_inputs(_stream(), _p(emb), _p(out), _ld(out), B, L, E), 'a4r_take_inputs')
 
 
 def adam_step(p, g, m, v, seg_end, seg_group, group_lr, step, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=1.0):
     require_gpu(p, g, m, v, seg_end, seg_group, group_lr)
-    _check(lib().a4r_adam_step(_stream(), _p(p), _p(g), _p(m), _p(v), C.c_int64(p.numel()), _p(seg_end), _p(seg_group),
-                               C.c_int(seg_end.numel()), _p(group_lr), C.c_int(step), C.c_float(beta1), C.c_float(beta2),
-                               C.c_float(eps), C.c_float(grad_scale)), 'a4r_adam_step')
+    _check(lib().a4r_adam_step(_stream(), _p(p), _p(g), _p(m), _p(v), p.numel(), _p(seg_end), _p(seg_group), seg_end.numel(), _p(group_lr), step, beta1, beta2, eps, grad_scale),
+           'a4r_adam_step')
 
 
 def _need(cond, what):
@@ -785,7 +807,7 @@ def grad_sumsq(g, partials, grad_scale=1.0):
     _need(partials.dtype == torch.float64 and partials.is_contiguous() and partials.numel() == GRAD_NORM_PARTS,
           f'grad_sumsq: partials must be contiguous fp64 with {GRAD_NORM_PARTS} elements')
     require_gpu(g, partials)
-    _check(lib().a4r_grad_sumsq(_stream(), _p(g), C.c_int64(g.numel()), C.c_float(grad_scale), _p(partials)), 'a4r_grad_sumsq')
+    _check(lib().a4r_grad_sumsq(_stream(), _p(g), g.numel(), grad_scale, _p(partials)), 'a4r_grad_sumsq')
 
 
 def adamw_step(p, g, m, v, seg_end, seg_group, group_lr, group_wd, step, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=1.0, decoupled=True,
@@ -813,21 +835,17 @@ def adamw_step(p, g, m, v, seg_end, seg_group, group_lr, group_wd, step, beta1=0
         _need(partials is not None, 'adamw_step: norm_out needs partials (the norm exists only when clipping)')
         _need(norm_out.dtype == torch.float32 and norm_out.numel() == 1, 'adamw_step: norm_out must be a one-element fp32 tensor')
     require_gpu(p, g, m, v, seg_end, seg_group, group_lr, group_wd, partials, norm_out)
-    _check(lib().a4r_adamw_step(_stream(), _p(p), _p(g), _p(m), _p(v), C.c_int64(n), _p(seg_end), _p(seg_group), C.c_int(seg_end.numel()),
-                                _p(group_lr), C.c_int(int(step)), C.c_float(beta1), C.c_float(beta2), C.c_float(eps), C.c_float(grad_scale),
-                                _p(group_wd), C.c_int(int(bool(decoupled))), _p(partials), C.c_float(max_norm if partials is not None else 0.0),
-                                _p(norm_out)),
-           'a4r_adamw_step')
+    _check(lib().a4r_adamw_step(_stream(), _p(p), _p(g), _p(m), _p(v), n, _p(seg_end), _p(seg_group), seg_end.numel(), _p(group_lr), int(step), beta1, beta2, eps, grad_scale,
+                                _p(group_wd), int(bool(decoupled)), _p(partials), max_norm if partials is not None else 0.0, _p(norm_out)), 'a4r_adamw_step')
 
 
 def pack_matrices(flat, desc_dev, n_desc, max_elems, dtype):
-    _check(lib().a4r_pack_matrices(_stream(), _p(flat), _p(desc_dev), C.c_int(n_desc), C.c_int(max_elems), C.c_int(dtype)),
-           'a4r_pack_matrices')
+    _check(lib().a4r_pack_matrices(_stream(), _p(flat), _p(desc_dev), n_desc, max_elems, dtype), 'a4r_pack_matrices')
 
 
 def topk_ws_bytes(U, N1, k):
     """Bytes of a4r_topk_items' workspace (a host-side query, no GPU); 0 for a shape the kernel refuses."""
-    return int(lib().a4r_topk_ws_bytes(C.c_int(U), C.c_int(N1), C.c_int(k)))
+    return int(lib().a4r_topk_ws_bytes(U, N1, k))
 
 
 def topk_items(prec, item_emb, excl_ptr, excl_idx, k, ids, scores):
@@ -862,15 +880,14 @@ def topk_items(prec, item_emb, excl_ptr, excl_idx, k, ids, scores):
     if excl_idx.numel() == 0:                 # (an empty list has no data pointer; the kernel reads no id of it)
         excl_idx = torch.zeros(1, dtype=torch.int32, device=prec.device)
     ws = torch.empty(topk_ws_bytes(U, N1, k), dtype=torch.uint8, device=prec.device)
-    _check(lib().a4r_topk_items(_stream(), _p(prec), _p(item_emb), _p(excl_ptr), _p(excl_idx), _p(ids), _p(scores), _p(ws),
-                                C.c_int(U), C.c_int(N1), C.c_int(E), C.c_int(k)), 'a4r_topk_items')
+    _check(lib().a4r_topk_items(_stream(), _p(prec), _p(item_emb), _p(excl_ptr), _p(excl_idx), _p(ids), _p(scores), _p(ws), U, N1, E, k), 'a4r_topk_items')
     return ids, scores
 
 
 def eval_rank(prec, item_emb, target, hist_ptr, hist_idx, rank):
     require_gpu(prec, item_emb, target, hist_ptr, hist_idx, rank)
-    _check(lib().a4r_eval_rank(_stream(), _p(prec), _p(item_emb), _p(target), _p(hist_ptr), _p(hist_idx), _p(rank),
-                               C.c_int(prec.shape[0]), C.c_int(item_emb.shape[0]), C.c_int(prec.shape[1])), 'a4r_eval_rank')
+    _check(lib().a4r_eval_rank(_stream(), _p(prec), _p(item_emb), _p(target), _p(hist_ptr), _p(hist_idx), _p(rank), prec.shape[0], item_emb.shape[0], prec.shape[1]),
+           'a4r_eval_rank')
 
 
 def id_sample(seqs, rows, item_num, seed, draw, negatives, ids, log_mask, err):
@@ -898,6 +915,5 @@ def id_sample(seqs, rows, item_num, seed, draw, negatives, ids, log_mask, err):
     if err.numel() != 1:
         raise ValueError('id_sample: err must hold one int32')
     require_gpu(seqs, rows, ids, log_mask, err)
-    _check(lib().a4r_id_sample(_stream(), _p(seqs), C.c_int(n_users), C.c_int(L), _p(rows), C.c_int(B), C.c_int(int(item_num)),
-                               C.c_uint64(int(seed) & (2 ** 64 - 1)), C.c_uint64(int(draw)), C.c_int(int(bool(negatives))),
-                               _p(ids), _p(log_mask), _p(err)), 'a4r_id_sample')
+    _check(lib().a4r_id_sample(_stream(), _p(seqs), n_users, L, _p(rows), B, int(item_num), int(seed) & (2 ** 64 - 1), int(draw), int(bool(negatives)), _p(ids), _p(log_mask),
+                               _p(err)), 'a4r_id_sample')

@@ -26,7 +26,7 @@ def lib():
     return None
 
 
-def require_gpu(*t):
+def require_gpu(*tensors):
     return None
 
 

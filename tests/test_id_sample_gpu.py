@@ -134,7 +134,6 @@ def test_errors_are_counted_and_the_neighbours_unaffected():
 
 def test_entry_refuses_bad_arguments_before_launching():
     """The library's own checks (the binding's are tested on the CPU): status -1, outputs untouched."""
-    import ctypes as C
     from adapter4rec_amd import _lib
     lib = _lib.lib()
     seqs, rows = torch.zeros(2, 21, dtype=torch.int32, device='cuda'), torch.zeros(4, dtype=torch.int32, device='cuda')
@@ -145,9 +144,8 @@ def test_entry_refuses_bad_arguments_before_launching():
     for bad in (dict(seqs=0), dict(rows=0), dict(ids=0), dict(mask=0), dict(err=0), dict(L=1), dict(L=257), dict(B=0), dict(n_users=0),
                 dict(item_num=0), dict(draw=2 ** 24)):
         a = dict(ok, **bad)
-        rc = lib.a4r_id_sample(C.c_void_p(0), C.c_void_p(a['seqs']), C.c_int(a['n_users']), C.c_int(a['L']), C.c_void_p(a['rows']), C.c_int(a['B']),
-                               C.c_int(a['item_num']), C.c_uint64(1), C.c_uint64(a['draw']), C.c_int(1), C.c_void_p(a['ids']),
-                               C.c_void_p(a['mask']), C.c_void_p(a['err']))
+        vals = (0, a['seqs'], a['n_users'], a['L'], a['rows'], a['B'], a['item_num'], 1, a['draw'], 1, a['ids'], a['mask'], a['err'])
+        rc = lib.a4r_id_sample(*(t(v) for t, v in zip(_lib.SIGNATURES['a4r_id_sample'][1], vals, strict=True)))
         assert rc == -1, bad
     torch.cuda.synchronize()
     assert (ids == GUARD_I).all() and (mask == GUARD_F).all() and int(err[0]) == GUARD_E

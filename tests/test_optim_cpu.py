@@ -380,9 +380,7 @@ def test_c_entries_return_einval_before_launching():
     buf = ctypes.create_string_buffer(1 << 16)                       # host memory: never dereferenced, the checks come first
     x = ctypes.cast(buf, P)
     f = lib.a4r_adamw_step
-    f.restype = ctypes.c_int
-    f.argtypes = [P, P, P, P, P, ctypes.c_int64, P, P, ctypes.c_int, P, ctypes.c_int, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
-                  P, ctypes.c_int, P, ctypes.c_float, P]
+    f.restype, f.argtypes = L.SIGNATURES['a4r_adamw_step']             # the binding's own declaration (tests/test_abi_cpu.py holds it to the header)
     base = [None, x, x, x, x, 8, x, x, 1, x, 1, 0.9, 0.999, 1e-8, 1.0, x, 1, x, 1.0, x]
     cases = {1: None, 2: None, 3: None, 4: None, 6: None, 7: None, 9: None, 15: None,             # NULL pointers
              5: 0, 8: 0, 10: 0}                                                                  # n <= 0, n_seg <= 0, step < 1
@@ -402,6 +400,5 @@ def test_c_entries_return_einval_before_launching():
     a[17] = None                                                     # norm_out without partials
     assert f(*a) == -1
     s = lib.a4r_grad_sumsq
-    s.restype = ctypes.c_int
-    s.argtypes = [P, P, ctypes.c_int64, ctypes.c_float, P]
+    s.restype, s.argtypes = L.SIGNATURES['a4r_grad_sumsq']
     assert s(None, None, 8, 1.0, x) == -1 and s(None, x, 8, 1.0, None) == -1 and s(None, x, 0, 1.0, x) == -1 and s(None, x, -3, 1.0, x) == -1

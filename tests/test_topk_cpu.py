@@ -33,8 +33,7 @@ def test_topk_null_and_shape_probes_return_einval():
     if torch.cuda.is_available():
         pytest.skip('argument-check probe is a CPU test')
     f = ctypes.CDLL(L.LIB_PATH).a4r_topk_items
-    f.argtypes = [ctypes.c_void_p] * 8 + [ctypes.c_int] * 4
-    f.restype = ctypes.c_int
+    f.restype, f.argtypes = L.SIGNATURES['a4r_topk_items']
     assert f(*([None] * 8), 0, 0, 0, 0) == -1
     buf = (ctypes.c_char * 4096)()
     p = ctypes.cast(buf, ctypes.c_void_p).value

@@ -164,8 +164,7 @@ def test_topk_argument_errors_launch_nothing():
     sc = torch.full((U, 257), 7.0, device=DEV)
     ws = torch.zeros(1 << 22, dtype=torch.uint8, device=DEV)
     f = lib.a4r_topk_items
-    f.argtypes = [C.c_void_p] * 8 + [C.c_int] * 4
-    f.restype = C.c_int
+    assert (f.restype, f.argtypes) == L.SIGNATURES['a4r_topk_items']      # installed by lib()
     P = lambda t, off=0: C.c_void_p(t.data_ptr() + off)
     for args in ((prec, 0, emb, 0, 128, 0), (prec, 0, emb, 0, 128, 257), (prec, 0, emb, 0, 96, 10), (prec, 4, emb, 0, 64, 10), (prec, 0, emb, 4, 64, 10)):
         p, po, e, eo, E, K = args
