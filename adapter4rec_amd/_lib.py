@@ -193,11 +193,13 @@ def lib():
                 f'{LIB_PATH} not found: build it with `python -c "import __graft_entry__ as g; g.build()"` '
                 '(hipcc --offload-arch=gfx950).  adapter4rec_amd has no CPU / PyTorch fallback.')
         _lib = C.CDLL(LIB_PATH)
-        missing = [name for name in SIGNATURES if not hasattr(_lib, name)]
+        from ._lib_ce_bf16 import SCORE_CE_BF16_SIGNATURES            # (the bf16 cross-entropy head's exports: a table of their own, bottom of this file)
+        tables = dict(SIGNATURES, **SCORE_CE_BF16_SIGNATURES)
+        missing = [name for name in tables if not hasattr(_lib, name)]
         if missing:                   # a build from before an entry point was added (additions keep the ABI number: no argument list changes)
             _lib = None
             raise RuntimeError(f'{LIB_PATH} lacks {", ".join(missing)}: rebuild it (make -C adapter4rec_amd/csrc)')
-        for name, (restype, argtypes) in SIGNATURES.items():
+        for name, (restype, argtypes) in tables.items():
             f = getattr(_lib, name)
             f.restype, f.argtypes = restype, argtypes
         got = _lib.a4r_version()
@@ -917,3 +919,17 @@ def id_sample(seqs, rows, item_num, seed, draw, negatives, ids, log_mask, err):
     require_gpu(seqs, rows, ids, log_mask, err)
     _check(lib().a4r_id_sample(_stream(), _p(seqs), n_users, L, _p(rows), B, int(item_num), int(seed) & (2 ** 64 - 1), int(draw), int(bool(negatives)), _p(ids), _p(log_mask),
                                _p(err)), 'a4r_id_sample')
+
+
+# The cross-entropy head on the bf16 MFMA (--ce_dtype bf16): declared in include/a4r_score_ce_bf16.h (which include/a4r.h includes) and bound in
+# _lib_ce_bf16.py with a signature table of its own, which lib() above checks and installs at load beside SIGNATURES.  Its wrappers and constants
+# are reachable under this module's name as well; they are resolved on first use, so either module can be imported first.
+_CE_BF16_NAMES = ('SCORE_CE_BF16_E', 'SCORE_CE_BF16_ROWS', 'SCORE_CE_BF16_SIGNATURES', 'cast_bf16', 'score_ce_bf16_bwd', 'score_ce_bf16_fwd',
+                  'score_ce_bf16_ranges', 'score_ce_bf16_ws_bytes')
+
+
+def __getattr__(name):
+    if name in _CE_BF16_NAMES:
+        from . import _lib_ce_bf16
+        return getattr(_lib_ce_bf16, name)
+    raise AttributeError(f'module {__name__!r} has no attribute {name!r}')

@@ -67,8 +67,9 @@ class _CVBase(nn.Module):
         self._native = [None]
         self._phm_owner = [None]
         self.compute_dtype = getattr(args, 'compute_dtype', 'bf16')
-        from ..engine_id import loss_flag
+        from ..engine_id import ce_dtype_flag, loss_flag
         self.loss = loss_flag(args, self.arch, use_modal)          # --loss: the ID tower's head (engine_id.py reads args.loss)
+        self.ce_dtype = ce_dtype_flag(args, self.loss)             # --ce_dtype: the number format of the --loss ce head (engine_id.py reads args.ce_dtype)
         if not use_modal:                        # model.py:33-35: the IDRec baseline's learned item table (engine_id.py)
             self.id_embedding = nn.Embedding(item_num + 1, args.embedding_dim, padding_idx=0)
             xavier_normal_(self.id_embedding.weight.data)

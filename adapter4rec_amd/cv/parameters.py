@@ -31,6 +31,7 @@ def parse_args(argv=None):
     p.add_argument('--min_seq_len', type=int, default=5)
     p.add_argument('--arch', type=str, default='sasrec')
     p.add_argument('--loss', type=str, default='bce', choices=['bce', 'ce'])   # --item_tower id: BCE against one sampled negative (the reference) or softmax cross-entropy over the whole table
+    p.add_argument('--ce_dtype', type=str, default='fp32', choices=['fp32', 'bf16'])   # --loss ce: the head's two products on the fp32 MFMA (the default) or on the bf16 MFMA over bf16 copies of its operands; --compute_dtype does not imply it
     p.add_argument('--use_scale', type=str, default='half')       # reference: fp16 autocast; here the engine's bf16 storage / fp32 accumulate
     p.add_argument('--n_tokens', type=int, default=10)
     p.add_argument('--num_workers', type=int, default=12)

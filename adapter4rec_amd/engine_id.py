@@ -26,6 +26,16 @@ def loss_flag(args, arch, use_modal):
     return loss
 
 
+def ce_dtype_flag(args, loss):
+    """args.ce_dtype ('fp32' when absent): the number format of the cross-entropy head's two products.  --compute_dtype does not imply it."""
+    ce_dtype = getattr(args, 'ce_dtype', 'fp32') or 'fp32'
+    if ce_dtype not in ('fp32', 'bf16'):
+        raise ValueError(f"--ce_dtype must be 'fp32' or 'bf16', got {ce_dtype!r}")
+    if ce_dtype == 'bf16' and loss != 'ce':
+        raise NotImplementedError('--ce_dtype bf16 without --loss ce: it selects the number format of the full-softmax head, the BCE head has one')
+    return ce_dtype
+
+
 class IdRecEngine(TransRecEngine):
     MULTI_ATTR = False
 
@@ -33,6 +43,7 @@ class IdRecEngine(TransRecEngine):
         if dtype == 'fp8':
             raise NotImplementedError('--compute_dtype fp8 with --item_tower id: the ID tower has no backbone GEMM to quantise')
         self.loss = loss_flag(args, arch, False)
+        self.ce_dtype = ce_dtype_flag(args, self.loss)
         super().__init__(model, args, arch=arch, dtype=dtype, phm_owner=phm_owner)
         self._err_pending, self._err_free = [], []           # (pinned host word, event) per step not yet checked; spare words
 
@@ -41,6 +52,8 @@ class IdRecEngine(TransRecEngine):
         self.item_num = w.shape[0] - 1
         if w.shape[1] != self.E or self.E % 4:
             raise NotImplementedError(f'ID table width {w.shape[1]} (embedding_dim {self.E}, a multiple of 4)')
+        if self.ce_dtype == 'bf16' and self.E not in L.SCORE_CE_BF16_E:
+            raise NotImplementedError(f'--ce_dtype bf16 with embedding_dim {self.E}: a4r_score_ce_bf16_* serves the widths {L.SCORE_CE_BF16_E}')
         if self.loss == 'ce' and self.E not in L.SCORE_CE_E:
             raise NotImplementedError(f'--loss ce with embedding_dim {self.E}: a4r_score_ce_* serves the widths {L.SCORE_CE_E}')
         self.H = self.E
@@ -162,7 +175,17 @@ class IdRecEngine(TransRecEngine):
     # ------------------------------------------------------------------ --loss ce: softmax cross-entropy over the whole table
     def _ce_ws(self, R):
         """The scratch a4r_score_ce_fwd and _bwd_rows share (ranges x R x E floats, whatever the table's size)."""
-        return self._buf('ce.ws', L.score_ce_ws_bytes(R, self.item_num + 1, self.E), 1, torch.uint8).view(-1)
+        ws_bytes = L.score_ce_bf16_ws_bytes if self.ce_dtype == 'bf16' else L.score_ce_ws_bytes
+        return self._buf('ce.ws', ws_bytes(R, self.item_num + 1, self.E), 1, torch.uint8).view(-1)
+
+    def _ce_cast(self, prec, R):
+        """--ce_dtype bf16: this step's bf16 copies of the head's operands, made once in the forward and read again by the backward.  The
+        table's copy ([item_num + 1, E] bf16, half a table) is the one buffer of the table's size the option adds."""
+        table_b = self._buf('ce.table_b', self.item_num + 1, self.E, torch.bfloat16)
+        prec_b = self._buf('ce.prec_b', R, self.E, torch.bfloat16)
+        L.cast_bf16(self.table, table_b)
+        L.cast_bf16(prec, prec_b, R * self.E)
+        return prec_b, table_b
 
     def _ce_forward(self, B, n_full, Mu, seed, train, lm, emb, prec, xin, ws, ix):
         """The head of train_forward under --loss ce: row (b, t) is trained against every item of the table with the positive id of position
@@ -173,10 +196,15 @@ class IdRecEngine(TransRecEngine):
         tgt.view(B, T).copy_(ix['rows'][:n_full].view(B, self.Lseq, 2)[:, 1:, 0])
         lse = self._buf('ce.lse', R, 1, torch.float32).view(-1)
         s_tgt = self._buf('ce.s_tgt', R, 1, torch.float32).view(-1)
-        L.score_ce_fwd(prec, self.table, tgt, lm.view(-1), lse, s_tgt, ws.view(-1), R, ws=self._ce_ws(R))
+        cast = None
+        if self.ce_dtype == 'bf16':
+            cast = self._ce_cast(prec, R)
+            L.score_ce_bf16_fwd(cast[0], cast[1], tgt, lm.view(-1), lse, s_tgt, ws.view(-1), R, ws=self._ce_ws(R))
+        else:
+            L.score_ce_fwd(prec, self.table, tgt, lm.view(-1), lse, s_tgt, ws.view(-1), R, ws=self._ce_ws(R))
         self._post_err(ix['err'])
         self._ctx = dict(B=B, n_items=n_full, n_full=n_full, M=0, Mu=Mu, seed=seed, train=train, lm=lm, emb=emb, prec=prec, xin=xin, tgt=tgt,
-                         lse=lse, ws=ws, saved_s=self._saved_sas, ix=ix)
+                         lse=lse, ws=ws, saved_s=self._saved_sas, ix=ix, ce_cast=cast)
         return ws[0, 0].clone()
 
     def _head_backward(self, c, grad_out, d_prec, d_emb, B):
@@ -186,6 +214,11 @@ class IdRecEngine(TransRecEngine):
             return super()._head_backward(c, grad_out, d_prec, d_emb, B)
         R = B * (self.Lseq - 1)
         L.zero(d_emb)
+        if c['ce_cast'] is not None:
+            prec_b, table_b = c['ce_cast']
+            L.score_ce_bf16_bwd(prec_b, table_b, c['tgt'], c['lm'].view(-1), c['lse'], c['ws'].view(-1), 1.0, d_prec,
+                                self.g_table() if self.g_table is not None else None, R, scale_dev=grad_out, ws=self._ce_ws(R))
+            return
         L.score_ce_bwd(c['prec'], self.table, c['tgt'], c['lm'].view(-1), c['lse'], c['ws'].view(-1), 1.0, d_prec,
                        self.g_table() if self.g_table is not None else None, R, scale_dev=grad_out, ws=self._ce_ws(R))
 

@@ -2,7 +2,7 @@
 """Throughput of the ID item tower (--item_tower id, the IDRec baseline) on its public path: optimizer.zero_grad(), model(ids, log_mask),
 loss.backward(), FusedAdam.step() -- one JSON line per configuration (ms/step, user-seq/s, and the inverted index's list lengths of a batch).
 
-    python tools/id_bench.py [--steps K] [--warmup W] [--only NAME] [--loss {bce,ce}]
+    python tools/id_bench.py [--steps K] [--warmup W] [--only NAME] [--loss {bce,ce}] [--ce_dtype {fp32,bf16}] [--skip_eager]
 
 Configurations (the reference's CV defaults: B 64, E 64, 2 blocks x 2 heads, Downstream/CV/parameters.py):
   full_L10 / full_L20     full histories at --max_seq_len 10 / 20, item_num 14 720 (the Amazon 2w catalogue), ids uniform
@@ -11,6 +11,8 @@ Configurations (the reference's CV defaults: B 64, E 64, 2 blocks x 2 heads, Dow
 --loss ce trains with the softmax cross-entropy over the whole table (a4r_score_ce_*) and adds, per configuration, a second JSON line that times
 the head alone (forward + both backward launches on the step's own rows and table) beside the same head in eager fp32 torch.matmul +
 F.cross_entropy (forward + backward), with torch.cuda.max_memory_allocated of each above what was allocated before it ran.
+--ce_dtype bf16 (with --loss ce) trains with the head on the bf16 MFMA (a4r_score_ce_bf16_*); the head-alone line then times those entry points,
+the two cast launches (table and rows) counted in fused_ms and reported on their own as cast_ms.  --skip_eager leaves the eager head out.
 Per-kernel times: run this under `rocprofv3 --kernel-trace --stats -- python tools/id_bench.py`."""
 import argparse
 import json
@@ -93,7 +95,7 @@ def _timed(fn, steps, warmup):
     return (time.perf_counter() - t0) / steps * 1e3, torch.cuda.max_memory_allocated() - base
 
 
-def head_compare(name, model, item_num, max_seq_len, steps, warmup):
+def head_compare(name, model, item_num, max_seq_len, steps, warmup, ce_dtype='fp32', skip_eager=False):
     """The cross-entropy head alone on B x max_seq_len rows against the model's table: the three fused launches beside eager fp32
     matmul + cross_entropy (forward and backward of both), same rows, same table, same targets."""
     from adapter4rec_amd import _lib as L
@@ -105,21 +107,35 @@ def head_compare(name, model, item_num, max_seq_len, steps, warmup):
     mask = torch.ones(R, device='cuda')
     lse, s_tgt, lw = torch.empty(R, device='cuda'), torch.empty(R, device='cuda'), torch.empty(4, device='cuda')
     d_prec, d_table = torch.empty(R, E, device='cuda'), torch.zeros(N1, E, device='cuda')
-    ranges = L.score_ce_ranges(R, N1)
-    ws = torch.empty(L.score_ce_ws_bytes(R, N1, E), dtype=torch.uint8, device='cuda')
+    bf16 = ce_dtype == 'bf16'
+    if bf16:
+        ranges = L.score_ce_bf16_ranges(R, N1)
+        ws = torch.empty(L.score_ce_bf16_ws_bytes(R, N1, E), dtype=torch.uint8, device='cuda')
+        prec_b, table_b = torch.empty(R, E, dtype=torch.bfloat16, device='cuda'), torch.empty(N1, E, dtype=torch.bfloat16, device='cuda')
+        head_fwd, head_bwd, a, b = L.score_ce_bf16_fwd, L.score_ce_bf16_bwd, prec_b, table_b
+    else:
+        ranges = L.score_ce_ranges(R, N1)
+        ws = torch.empty(L.score_ce_ws_bytes(R, N1, E), dtype=torch.uint8, device='cuda')
+        head_fwd, head_bwd, a, b = L.score_ce_fwd, L.score_ce_bwd, prec, table
+
+    def cast():
+        L.cast_bf16(table, table_b)
+        L.cast_bf16(prec, prec_b)
 
     def fwd():
-        L.score_ce_fwd(prec, table, tgt, mask, lse, s_tgt, lw, R, ws=ws)
+        head_fwd(a, b, tgt, mask, lse, s_tgt, lw, R, ws=ws)
 
     def rows():
-        L.score_ce_bwd(prec, table, tgt, mask, lse, lw, 1.0, d_prec, None, R, ws=ws)
+        head_bwd(a, b, tgt, mask, lse, lw, 1.0, d_prec, None, R, ws=ws)
 
     def items():
-        L.score_ce_bwd(prec, table, tgt, mask, lse, lw, 1.0, None, d_table, R)
+        head_bwd(a, b, tgt, mask, lse, lw, 1.0, None, d_table, R)
 
     def fused():
+        if bf16:
+            cast()
         fwd()
-        L.score_ce_bwd(prec, table, tgt, mask, lse, lw, 1.0, d_prec, d_table, R, ws=ws)
+        head_bwd(a, b, tgt, mask, lse, lw, 1.0, d_prec, d_table, R, ws=ws)
 
     pe, te, tl = prec.clone().requires_grad_(True), table.clone().requires_grad_(True), tgt.long() - 1
 
@@ -130,21 +146,24 @@ def head_compare(name, model, item_num, max_seq_len, steps, warmup):
         return loss
 
     fused_ms, fused_peak = _timed(fused, steps, warmup)
-    eager_ms, eager_peak = _timed(eager, steps, warmup)
+    eager_ms, eager_peak = (0.0, 0) if skip_eager else _timed(eager, steps, warmup)
     flop = 2.0 * R * item_num * E                          # one streamed product; forward 1, bwd_rows 2, bwd_items 2
     parts = {}
     for nm, fn, k in (('fwd', fwd, 1), ('bwd_rows', rows, 2), ('bwd_items', items, 2)):
         ms, _ = _timed(fn, steps, warmup)
         parts[nm + '_ms'] = round(ms, 4)
-        parts[nm + '_mfma_fraction'] = round(k * flop / (ms * 1e-3) / FP32_MFMA_PEAK, 4)
-    return dict(config=name + '_ce_head', rows=R, item_num=item_num, embedding_dim=E, ranges=ranges, steps=steps, warmup=warmup,
+        parts[nm + '_mfma_fraction'] = round(k * flop / (ms * 1e-3) / FP32_MFMA_PEAK, 4)      # (of the fp32 peak under either --ce_dtype: one scale)
+    if bf16:
+        parts['cast_ms'] = round(_timed(cast, steps, warmup)[0], 4)
+        parts['table_bf16_bytes'] = int(table_b.numel() * 2)
+    return dict(config=name + '_ce_head', ce_dtype=ce_dtype, rows=R, item_num=item_num, embedding_dim=E, ranges=ranges, steps=steps, warmup=warmup,
                 fused_ms=round(fused_ms, 4), eager_ms=round(eager_ms, 4), fused_peak_bytes=int(fused_peak), eager_peak_bytes=int(eager_peak),
                 fused_ws_bytes=int(ws.numel()), logits_bytes=int(R * item_num * 4),
                 fused_tflops_5_products=round(5 * flop / (fused_ms * 1e-3) / 1e12, 2), **parts,
-                loss_fused=float(lw[0]), loss_eager=float(eager().detach()))
+                loss_fused=float(lw[0]), loss_eager=None if skip_eager else float(eager().detach()))
 
 
-def run(name, max_seq_len, item_num, steps, warmup, loss_kind='bce'):
+def run(name, max_seq_len, item_num, steps, warmup, loss_kind='bce', ce_dtype='fp32'):
     from adapter4rec_amd.cv import Model
     from adapter4rec_amd.cv.inject import optimizer_groups
     from adapter4rec_amd.optim import FusedAdam
@@ -152,6 +171,7 @@ def run(name, max_seq_len, item_num, steps, warmup, loss_kind='bce'):
     rng = np.random.default_rng(0)
     args = model_args(max_seq_len)
     args.loss = loss_kind
+    args.ce_dtype = ce_dtype
     args.lr, args.fine_tune_lr, args.adapter_cv_lr, args.adapter_sasrec_lr = 1e-4, 1e-4, 1e-4, 1e-4
     model = Model(args, item_num, False).to('cuda')
     model.train()
@@ -177,7 +197,7 @@ def run(name, max_seq_len, item_num, steps, warmup, loss_kind='bce'):
         loss = step(i)
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / steps
-    out = dict(config=name, loss_kind=loss_kind, batch=B, embedding_dim=E, max_seq_len=max_seq_len, item_num=item_num, steps=steps, warmup=warmup,
+    out = dict(config=name, loss_kind=loss_kind, ce_dtype=ce_dtype, batch=B, embedding_dim=E, max_seq_len=max_seq_len, item_num=item_num, steps=steps, warmup=warmup,
                 ms_per_step=round(dt * 1e3, 4), user_seq_per_s=round(B / dt, 1), loss=float(loss.detach()),
                 longest_list_max=max(s['longest_list'] for s in lens), median_list_median=float(np.median([s['median_list'] for s in lens])),
                 first_batch=stats)
@@ -193,14 +213,16 @@ def main():
     ap.add_argument('--warmup', type=int, default=20)
     ap.add_argument('--only', default=None)
     ap.add_argument('--loss', default='bce', choices=['bce', 'ce'])
+    ap.add_argument('--ce_dtype', default='fp32', choices=['fp32', 'bf16'])
+    ap.add_argument('--skip_eager', action='store_true')
     a = ap.parse_args()
     for name, msl, n in CONFIGS:
         if a.only and name != a.only:
             continue
-        line, model = run(name, msl, n, a.steps, a.warmup, a.loss)
+        line, model = run(name, msl, n, a.steps, a.warmup, a.loss, a.ce_dtype)
         print(json.dumps(line), flush=True)
         if a.loss == 'ce':
-            print(json.dumps(head_compare(name, model, n, msl, a.steps, a.warmup)), flush=True)
+            print(json.dumps(head_compare(name, model, n, msl, a.steps, a.warmup, a.ce_dtype, a.skip_eager)), flush=True)
 
 
 if __name__ == '__main__':
