@@ -210,11 +210,16 @@ def adapter_ln_bwd(dy, v, stats, gamma, dres, zp, act, WuT, WdT, inner_res, dv, 
         if dbias is not None:
             dbias += g.sum(0)
         dv[:M] = g.to(dv.dtype)
+    elif bias_total and dbias is not None and dres is not None:
+        # dbias = sums of dv AFTER dres is added, from the fp32 values before their bf16 store, as in the kernel (sv += d8 ahead of the pack)
+        g32 = torch.zeros(M, dv.shape[1])
+        ln_bwd(dy, v, stats, gamma, g32, M=M, dgamma=dgamma, dbeta=dbeta)
+        g32 += dres[:M].float()
+        dbias += g32.sum(0)
+        dv[:M] = g32.to(dv.dtype)
     else:
-        ln_bwd(dy, v, stats, gamma, dv, M=M, dgamma=dgamma, dbeta=dbeta, dbias=None if bias_total else dbias, dres=dres)
+        ln_bwd(dy, v, stats, gamma, dv, M=M, dgamma=dgamma, dbeta=dbeta, dbias=dbias, dres=dres)
     dq = dv[:M].float()
-    if bias_total and dbias is not None:
-        dbias += dq.sum(0)
     dz = (dq @ WuT.float().t()) * _dact(zp[:M].float(), act)
     dzp[:M] = dz.to(dzp.dtype)
     if dbd is not None:

@@ -1226,6 +1226,75 @@ def test_adapter_ln_rejects():
     third = mk(128)
     with pytest.raises(RuntimeError):                                      # three distinct streamed tensors
         L.adapter_ln_fwd(a, o, third, Wd, bd, Wu, bu, gamma, beta, 1e-12, 1, mk(64), mk(64), mk(128), mk(128), torch.zeros(64, 2, device=dev()))
+    # every other argument check of the two entry points (host side: nothing is launched): each call differs from a valid one in ONE respect, must
+    # raise, and leaves the sentinel-filled outputs as they were
+    S, M = -768.0, 64
+
+    def args(H=128, d=64, dt=t):
+        a, o, Wd, Wu, bd, bu, gamma, beta = _adapter_case(H, M)
+        k = dict(a=a.to(dt), o=o.to(dt), Wd=Wd[:d].contiguous().to(dt), Wu=Wu[:, :d].contiguous().to(dt), bd=bd[:d].contiguous(), bu=bu, gamma=gamma, beta=beta)
+        full = lambda r, c, dtype=dt, s=S: torch.full((r, c), s, dtype=dtype, device=dev())
+        k.update(zp=full(M, 64), z=full(M, 64), v=full(M, H), y=full(M, H), st=full(M, 2, torch.float32), dv=full(M, H), dzp=full(M, 64), dh=full(M, H),
+                 dg=full(1, H, torch.float32)[0], dbi=full(1, H, torch.float32)[0], y8=full(M, H, torch.uint8, 0xA5), ys=full(1, M, torch.float32)[0],
+                 p4=full(M, H // 2, torch.int8, -77), dy=a.to(dt), vin=o.to(dt), zpin=rnd(M, 64, dtype=dt, seed=5), dres=rnd(M, H, dtype=dt, seed=6),
+                 stin=torch.ones(M, 2, device=dev()))
+        return k
+    outs = ('zp', 'z', 'v', 'y', 'st', 'dv', 'dzp', 'dh', 'dg', 'dbi', 'ys')
+
+    def fwd(k, **kw):
+        p = dict(dict(A=k['a'], R1=k['a'], R2=k['o'], zp=k['zp'], z=k['z'], v=k['v'], y=k['y'], M=None, extra={}), **kw)
+        L.adapter_ln_fwd(p['A'], p['R1'], p['R2'], k['Wd'], k['bd'], k['Wu'], k['bu'], k['gamma'], k['beta'], 1e-12, 1, p['zp'], p['z'], p['v'], p['y'], k['st'],
+                         M=p['M'], **p['extra'])
+
+    def bwd(k, **kw):
+        p = dict(dict(dy=k['dy'], v=k['vin'], dres=None, dv=k['dv'], dh=k['dh'], M=None, extra={}), **kw)
+        L.adapter_ln_bwd(p['dy'], p['v'], k['stin'], k['gamma'], p['dres'], k['zpin'], 1, k['Wu'].t().contiguous(), k['Wd'].t().contiguous(), True,
+                         p['dv'], k['dzp'], p['dh'], M=p['M'], **p['extra'])
+
+    def rejected(k, call, what, **kw):
+        with pytest.raises(RuntimeError):
+            call(k, **kw)
+        torch.cuda.synchronize()
+        for nm in outs:
+            assert bool((k[nm] == S).all()), f'{what}: {nm} was written'
+        assert bool((k['y8'] == 0xA5).all()) and bool((k['p4'] == -77).all()), f'{what}: a byte output was written'
+
+    k = args()
+    fwd(k)                                                                 # the base call IS valid (and so is its backward)
+    bwd(k)
+    assert not bool((k['y'] == S).any()) and not bool((k['dh'] == S).any())
+    wide = lambda x, extra, off=0: torch.cat([x, torch.zeros(x.shape[0], extra, dtype=x.dtype, device=dev())], 1)[:, off:off + x.shape[1]]
+    for call in (fwd, bwd):
+        nm = call.__name__
+        rejected(args(), call, f'{nm} M % 16', M=40)
+        rejected(args(), call, f'{nm} M = 0', M=0)
+        rejected(args(d=32), call, f'{nm} d != 64')
+        rejected(args(dt=torch.float32), call, f'{nm} fp32 operands')
+    k = args()
+    rejected(k, fwd, 'fwd lda % 8', A=wide(k['a'], 4), R1=k['o'], R2=None)
+    k = args()
+    rejected(k, fwd, 'fwd ldy % 8', y=torch.full((M, 132), S, dtype=t, device=dev())[:, :128])
+    k = args()
+    rejected(k, fwd, 'fwd A off by 4 elements', A=wide(k['a'], 8, 4), R1=k['o'], R2=None)
+    k = args()
+    rejected(k, fwd, 'fwd v off by 4 elements', v=torch.full((M, 136), S, dtype=t, device=dev())[:, 4:132])
+    k = args()
+    rejected(k, bwd, 'bwd lddy % 8', dy=wide(k['dy'], 4))
+    k = args()
+    rejected(k, bwd, 'bwd dres off by 4 elements', dres=wide(k['dres'], 8, 4))
+    k = args()
+    rejected(k, bwd, 'bwd dh off by 4 elements', dh=torch.full((M, 136), S, dtype=t, device=dev())[:, 4:132])
+    rejected(args(H=1024), bwd, 'bwd H = 1024')
+    k = args()
+    rejected(k, bwd, 'beta_y with dres', dres=k['dres'], extra=dict(beta_y=k['beta']))
+    k = args()
+    rejected(k, bwd, 'beta_y with dgamma', extra=dict(beta_y=k['beta'], dgamma=k['dg']))
+    k = args()
+    bwd(k, extra=dict(beta_y=k['beta'], dbias=k['dbi']))                    # (beta_y alone, with dbias, is an instantiation)
+    k = args()
+    rejected(k, fwd, 'y8 without ys', extra=dict(y8=k['y8']))
+    k = args()
+    rejected(k, fwd, 'nibble plane with ld < H / 2', extra=dict(y32=k['p4'].as_strided((M, 64), (60, 1))))
 
 
 # ------------------------------------------------------------------ fp8 (OCP e4m3fn) operands
