@@ -2,14 +2,13 @@
 // materialising the [users, items] score matrix and without the per-user Python loop.
 //
 // rank[u] = 1 + #{ i in [1, N1) : i not in hist(u), score(u, i) > score(u, target[u]) }.
-// A workgroup owns 16 users; their vectors are the A operand (kept in registers) of fp32 MFMA
-// 16x16x4 tiles whose B operand streams 16 items at a time straight from global memory (the item
-// table is read once per 16 users; it is L2/Infinity-Cache resident).  The target's score is
-// produced by the very same instruction sequence (B rows = the 16 users' target items, diagonal
-// taken), so the comparison is bit-consistent.  History items are excluded by counting every item first and taking back the user's
+// A workgroup owns 16 users and walks the table by the item-table score sweep (a4r_score_sweep.h),
+// fp32, requested one tile ahead (the item table is read once per 16 users; it is L2/Infinity-Cache
+// resident).  The target's score is produced by the very same instruction sequence (B rows = the
+// 16 users' target items, diagonal taken), so the comparison is bit-consistent.  History items are excluded by counting every item first and taking back the user's
 // (<= A4R_EVAL_MAX_HISTORY, distinct) history ids that beat the target -- their scores from the same instruction sequence again.  fp32 throughout: ranks are integers (bit-exact
 // against the oracle up to fp32 summation order of the 64-term dot products).
-#include "a4r_common.h"
+#include "a4r_score_sweep.h"
 #include "../../include/a4r.h"
 
 namespace {
@@ -34,20 +33,14 @@ __global__ void __launch_bounds__(256) eval_rank_kernel(const float* __restrict_
         for (int j = tid & 15; j < n; j += 16) hist[ul][j] = hist_idx[b + j];
         if ((tid & 15) == 0) { nhist[ul] = n; cnt[ul] = 0; }
     }
-    // A operand: 16 users x E, lane (user r16, kg) holds chunk (ks*4 + kg)
-    uint4 ua[KS];
+    uint4 ua[KS];                                    // A operand: the 16 users
     const int urow = min(u0 + r16, U - 1);
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) ua[ks] = *reinterpret_cast<const uint4*>(prec + (size_t)urow * E + (ks * 4 + kg) * 4);
+    frag_load<E>(ua, prec, urow, kg);
     // target scores: B rows = target items of the 16 users, keep the diagonal
     {
-        const int trow = target[urow];
-        f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-            const uint4 b = *reinterpret_cast<const uint4*>(item_emb + (size_t)trow * E + (ks * 4 + kg) * 4);
-            Mma<float>::mma(ua[ks], b, acc);
-        }
+        uint4 b[KS];
+        frag_load<E>(b, item_emb, target[urow], kg);
+        const f32x4_t acc = score_tile<float>(ua, b);
         // element (row = kg*4 + rr, col = r16): diagonal where kg*4 + rr == r16
         if (wave == 0) {
 #pragma unroll
@@ -60,9 +53,9 @@ __global__ void __launch_bounds__(256) eval_rank_kernel(const float* __restrict_
 #pragma unroll
     for (int rr = 0; rr < 4; ++rr) ts[rr] = tscore[kg * 4 + rr];
     int local[4] = {0, 0, 0, 0};
-    // items 1 .. N1-1 in tiles of 16; the 4 waves of the block take every 4th tile
-    // The item fragments of the NEXT tile are requested before this tile's products (round 6): the table comes from L2 / the Infinity Cache at 500+ cycles a
-    // request, and with one tile in flight per wave the launch ran at 0.23 of the fp32 MFMA rate -- waiting, not streaming (profiles/r06_e_eval_host.txt).
+    // The sweep itself -- the deal, the request one tile ahead and the score tile of a4r_score_sweep.h, as topk_partial_kernel runs them -- is
+    // written out here: through SweepDeal / sweep_next / score_tile this loop gave the same bits but, the compiler scheduling it another
+    // way, a launch 9 % slower at E = 128 (and 22 % faster at E = 64); piece by piece it ran up to twice as long (profiles/LOG.md).
     const int ntiles = (N1 - 1 + 15) / 16, tstep = gridDim.y * 4;
     int t = blockIdx.y * 4 + wave;
     uint4 bn[KS];
@@ -101,12 +94,9 @@ __global__ void __launch_bounds__(256) eval_rank_kernel(const float* __restrict_
             bool ok = h >= 1 && h < N1 && u0 + r16 < U;
             for (int k = 0; k < j && ok; ++k) ok = hist[r16][k] != h;          // first occurrence only
             const int hrow = ok ? h : 0;
-            f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) {
-                const uint4 b = *reinterpret_cast<const uint4*>(item_emb + (size_t)hrow * E + (ks * 4 + kg) * 4);
-                Mma<float>::mma(ua[ks], b, acc);
-            }
+            uint4 b[KS];
+            frag_load<E>(b, item_emb, hrow, kg);
+            const f32x4_t acc = score_tile<float>(ua, b);
 #pragma unroll
             for (int rr = 0; rr < 4; ++rr)
                 if (kg * 4 + rr == r16 && ok && acc[rr] > ts[rr]) atomicSub(&cnt[r16], 1);
@@ -132,17 +122,12 @@ __global__ void fill_i32_kernel(int32_t* p, int n, int v) {
 extern "C" int a4r_eval_rank(void* stream, const float* prec, const float* item_emb, const int32_t* target,
                              const int32_t* hist_ptr, const int32_t* hist_idx, int32_t* rank, int U, int N1, int E) {
     if (!prec || !item_emb || !target || !hist_ptr || !hist_idx || !rank || U <= 0 || N1 < 2) return A4R_EINVAL;
-    if (E != 64 && E != 128 && E != 256 && E != 512) return A4R_EINVAL;
-    if ((reinterpret_cast<uintptr_t>(prec) | reinterpret_cast<uintptr_t>(item_emb)) & 15u) return A4R_EINVAL;
+    if (!width_served(WidthsF32{}, E) || !aligned16(prec, item_emb)) return A4R_EINVAL;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(fill_i32_kernel, dim3((U + 255) / 256), dim3(256), 0, s, rank, U, 1);
-    const int gx = (U + 15) / 16;
-    int gy = 2048 / gx; if (gy < 1) gy = 1;
-    const int ntiles = (N1 - 1 + 15) / 16;
-    if (gy > (ntiles + 3) / 4) gy = (ntiles + 3) / 4;
-    if (E == 64) hipLaunchKernelGGL(eval_rank_kernel<64>, dim3(gx, gy), dim3(256), 0, s, prec, item_emb, target, hist_ptr, hist_idx, rank, U, N1);
-    else if (E == 128) hipLaunchKernelGGL(eval_rank_kernel<128>, dim3(gx, gy), dim3(256), 0, s, prec, item_emb, target, hist_ptr, hist_idx, rank, U, N1);
-    else if (E == 256) hipLaunchKernelGGL(eval_rank_kernel<256>, dim3(gx, gy), dim3(256), 0, s, prec, item_emb, target, hist_ptr, hist_idx, rank, U, N1);
-    else hipLaunchKernelGGL(eval_rank_kernel<512>, dim3(gx, gy), dim3(256), 0, s, prec, item_emb, target, hist_ptr, hist_idx, rank, U, N1);
+    const dim3 grid((U + 15) / 16, sweep_ranges(U, N1));
+    with_width(WidthsF32{}, E, [&](auto e) {
+        hipLaunchKernelGGL(eval_rank_kernel<decltype(e)::value>, grid, dim3(256), 0, s, prec, item_emb, target, hist_ptr, hist_idx, rank, U, N1);
+    });
     return a4r_launch_status();
 }

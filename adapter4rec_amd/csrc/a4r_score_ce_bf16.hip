@@ -1,7 +1,7 @@
 // The full-softmax cross-entropy head of the ID tower on the bf16 MFMA (--ce_dtype bf16): the function of a4r_score_ce.hip evaluated at
 // prec_b = bf16(prec), table_b = bf16(table) (round to nearest even; a4r_score_ce_bf16_cast writes the two copies), scores accumulated in fp32.
 //
-//   s[r, i] = <prec_b[r], table_b[i]>, i = 1 .. N1-1;  lse, s_tgt, loss, count, trained(r), w[r] as a4r_score_ce.hip states them
+//   s[r, i] = <prec_b[r], table_b[i]>, i = 1 .. N1-1;  lse, s_tgt, loss, count, trained(r), w[r] as a4r_score_ce_common.h states them
 //   d_prec[r]  = g w[r] (sum_i p[r, i] table_b[i] - table_b[tgt_r])                 (straight-through: handed to the fp32 masters as it is)
 //   d_table[i] += g sum_r w[r] (p[r, i] - [i == tgt_r]) prec_b[r]
 //
@@ -10,7 +10,8 @@
 // fragments (8 VGPRs a tile at E = 64) -- and a 16-item tile's B fragments, loaded once, meet all four: a quarter of the table passes at half
 // the bytes a pass.  One v_mfma_f32_16x16x32_bf16 covers K = 32 (a lane's 16-byte chunk is 8 elements, k = 8 (lane >> 4) + j).
 //
-// Forward: as ce_fwd_kernel, four row tiles wide.  Range merge: the same one-workgroup launch.
+// Scores: the item-table score sweep of a4r_score_sweep.h at T = bf16_t.  Forward: the online update and the reduce-and-store of
+// a4r_score_ce_common.h, four row tiles wide.  Range merge and the d_prec finish: the launches of that header.
 // Backward, rows:  the score tiles of TWO 16-item tiles are formed transposed (items as A, rows as B): a lane then holds p[row = lane & 15] for
 //   the items 4 kg + reg of either tile, which is the K = 32 A fragment of the second product under the contraction order
 //       slot 8 kg + j  <->  item 32 u + 16 (j >> 2) + 4 kg + (j & 3) of pair u        (a permutation of the pair's 32 items)
@@ -23,35 +24,13 @@
 //   has too few tiles to give every SIMD a wave otherwise).  Every table row is written by exactly one wave, once.
 // No float atomics, a fixed schedule: the same inputs give the same bits.  Nothing of size rows x items is written.  E = 64 and 128: at 256 the
 // backward's G x E output accumulators alone are 256 registers a lane beside the 128 of the row tiles.
-#include "a4r_common.h"
-#include "../../include/a4r.h"
+#include "a4r_score_ce_common.h"
 
 namespace {
 
-constexpr int MAX_RANGES = A4R_SCORE_CE_MAX_RANGES;
 constexpr int G = A4R_SCORE_CE_BF16_ROWS;
 constexpr int RT = G / 16;
 constexpr int ITEMS_WIDE_TILES = 8192;      // 131 072 items: from here a wave of the item launch owns 4 tiles
-
-A4R_DEV void lse_merge(float& m, float& l, float m2, float l2) {       // (as a4r_score_ce.hip: an empty set is (-inf, 0))
-    const float mn = fmaxf(m, m2);
-    const float a = m == mn ? l : l * __expf(m - mn);
-    const float b = m2 == mn ? l2 : l2 * __expf(m2 - mn);
-    m = mn;
-    l = a + b;
-}
-
-A4R_DEV bool ce_trained(const float* __restrict__ log_mask, int tg, int r, int N1) { return log_mask[r] != 0.f && tg >= 1 && tg < N1; }
-
-A4R_DEV float ce_gw(const float* __restrict__ loss_ws, float loss_scale, const float* __restrict__ loss_scale_dev) {
-    const float cnt = loss_ws[2];
-    return cnt > 0.f ? loss_scale * (loss_scale_dev ? loss_scale_dev[0] : 1.f) / cnt : 0.f;
-}
-
-// the 16-byte chunk (lane >> 4) of K step ks of a bf16 row
-template <int E> A4R_DEV uint4 ld_chunk(const bf16_t* __restrict__ base, int row, int ks, int kg) {
-    return *reinterpret_cast<const uint4*>(base + (size_t)row * E + ks * 32 + kg * 8);
-}
 
 // 8 dwords (one per contraction slot, each two neighbouring bf16 columns) -> the B fragments of the even and of the odd column
 A4R_DEV uint4 frag_lo(const unsigned (&w)[8]) {
@@ -92,9 +71,7 @@ __global__ void __launch_bounds__(256) ceb_fwd_kernel(const bf16_t* __restrict__
     float m[RT][4], l[RT][4], st[RT][4];
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt) {
-        const int urow = min(r0 + rt * 16 + r16, R - 1);
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) ua[rt][ks] = ld_chunk<E>(prec, urow, ks, kg);
+        frag_load<E>(ua[rt], prec, min(r0 + rt * 16 + r16, R - 1), kg);
 #pragma unroll
         for (int rr = 0; rr < 4; ++rr) {
             const int row = r0 + rt * 16 + kg * 4 + rr;
@@ -102,95 +79,23 @@ __global__ void __launch_bounds__(256) ceb_fwd_kernel(const bf16_t* __restrict__
             m[rt][rr] = -__builtin_huge_valf(); l[rt][rr] = 0.f; st[rt][rr] = 0.f;
         }
     }
-    const int ntiles = (N1 - 1 + 15) / 16, tstep = gridDim.y * 4;
-    int t = blockIdx.y * 4 + wave;
+    const SweepDeal<> deal(N1, wave);
     uint4 bn[KS];
-    {
-        const int irow = min(1 + min(t, ntiles - 1) * 16 + r16, N1 - 1);
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) bn[ks] = ld_chunk<E>(table, irow, ks, kg);
-    }
-    for (; t < ntiles; t += tstep) {
+    sweep_begin<E, true>(bn, table, deal, r16, kg);
+    for (int t = deal.first; t < deal.ntiles; t += deal.tstep) {
         const int i = 1 + t * 16 + r16;                 // this lane's item column
         uint4 b[KS];
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) b[ks] = bn[ks];
-        const int irow = min(1 + min(t + tstep, ntiles - 1) * 16 + r16, N1 - 1);          // (past the end: the last tile again, never used)
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) bn[ks] = ld_chunk<E>(table, irow, ks, kg);
+        sweep_next<E, true>(b, bn, table, deal, t, r16, kg);
 #pragma unroll
         for (int rt = 0; rt < RT; ++rt) {
-            f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) Mma<bf16_t>::mma(ua[rt][ks], b[ks], acc);
+            const f32x4_t acc = score_tile<bf16_t>(ua[rt], b);
             if (i < N1) {
 #pragma unroll
-                for (int rr = 0; rr < 4; ++rr) {
-                    const float s = acc[rr], d = s - m[rt][rr];         // one exp per score, as ce_fwd_kernel
-                    const float e = __expf(-fabsf(d));
-                    if (d > 0.f) { l[rt][rr] = l[rt][rr] * e + 1.f; m[rt][rr] = s; } else l[rt][rr] += e;
-                    if (i == tg[rt][rr]) st[rt][rr] = s;
-                }
+                for (int rr = 0; rr < 4; ++rr) ce_online(acc[rr], i == tg[rt][rr], m[rt][rr], l[rt][rr], st[rt][rr]);
             }
         }
     }
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr) {
-#pragma unroll
-            for (int o = 8; o > 0; o >>= 1) {           // over the 16 item columns (the target's score sits in one lane: the others add 0)
-                const float m2 = __shfl_xor(m[rt][rr], o, 64), l2 = __shfl_xor(l[rt][rr], o, 64);
-                lse_merge(m[rt][rr], l[rt][rr], m2, l2);
-                st[rt][rr] += __shfl_xor(st[rt][rr], o, 64);
-            }
-            if (r16 == 0) {
-                float* o = red[wave][rt * 16 + kg * 4 + rr];
-                o[0] = m[rt][rr]; o[1] = l[rt][rr]; o[2] = st[rt][rr];
-            }
-        }
-    __syncthreads();
-    if (tid < G && r0 + tid < R) {
-        float mm = red[0][tid][0], ll = red[0][tid][1], ss = red[0][tid][2];
-#pragma unroll
-        for (int w = 1; w < 4; ++w) { lse_merge(mm, ll, red[w][tid][0], red[w][tid][1]); ss += red[w][tid][2]; }
-        float* o = ws + ((size_t)blockIdx.y * R + r0 + tid) * 4;
-        o[0] = mm; o[1] = ll; o[2] = ss;
-    }
-}
-
-// one workgroup: the ranges of every row in range order -> lse, s_tgt; the trained rows counted, their losses summed in fp64 in a fixed order
-__global__ void __launch_bounds__(256) ceb_merge_kernel(const float* __restrict__ ws, const int32_t* __restrict__ tgt,
-                                                        const float* __restrict__ log_mask, float* __restrict__ lse, float* __restrict__ s_tgt,
-                                                        float* __restrict__ loss_ws, int R, int N1, int gy) {
-    __shared__ double wsum[4];
-    __shared__ int wcnt[4];
-    const int tid = threadIdx.x;
-    double sum = 0.0;
-    int cnt = 0;
-    for (int r = tid; r < R; r += 256) {
-        float m = -__builtin_huge_valf(), l = 0.f, st = 0.f;
-        for (int y = 0; y < gy; ++y) {
-            const float* p = ws + ((size_t)y * R + r) * 4;
-            lse_merge(m, l, p[0], p[1]);
-            st += p[2];
-        }
-        const float v = m + logf(l);
-        lse[r] = v;
-        s_tgt[r] = st;
-        if (ce_trained(log_mask, tgt[r], r, N1)) { sum += (double)v - (double)st; ++cnt; }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { sum += __shfl_xor(sum, o, 64); cnt += __shfl_xor(cnt, o, 64); }
-    if ((tid & 63) == 0) { wsum[tid >> 6] = sum; wcnt[tid >> 6] = cnt; }
-    __syncthreads();
-    if (tid == 0) {
-        const double tot = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
-        const int n = wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
-        loss_ws[0] = n ? (float)(tot / n) : 0.f;
-        loss_ws[1] = n ? (float)tot : 0.f;
-        loss_ws[2] = (float)n;
-    }
+    ce_reduce_store<G>(m, l, st, red, ws, R, r0);
 }
 
 template <int E>
@@ -208,37 +113,37 @@ __global__ void __launch_bounds__(256) ceb_bwd_rows_kernel(const bf16_t* __restr
     for (int rt = 0; rt < RT; ++rt) {
         const int urow = min(r0 + rt * 16 + r16, R - 1);
 #pragma unroll
-        for (int ks = 0; ks < KS; ++ks) ua[rt][ks] = ld_chunk<E>(prec, urow, ks, kg);
+        for (int ks = 0; ks < KS; ++ks) ua[rt][ks] = frag_chunk<E>(prec, urow, ks, kg);
         lse_r[rt] = lse[urow];
 #pragma unroll
         for (int n = 0; n < NT; ++n) d[rt][n] = f32x4_t{0.f, 0.f, 0.f, 0.f};
     }
-    const int npairs = (N1 - 1 + 31) / 32, ustep = gridDim.y * 4;
-    int u = blockIdx.y * 4 + wave;
+    // The sweep in pairs of 16-item tiles (lane column 16 h + r16 of pair u), chunk by chunk in this kernel's own loops: through frag_load /
+    // sweep_next the compiler schedules the loop another way, and it ran 27 % slower at 500 000 items (profiles/LOG.md)
+    const SweepDeal<32> deal(N1, wave);
     uint4 bn[2][KS];
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
-        const int irow = min(1 + min(u, npairs - 1) * 32 + h * 16 + r16, N1 - 1);
+        const int irow = deal.row(deal.first, h * 16 + r16);
 #pragma unroll
-        for (int ks = 0; ks < KS; ++ks) bn[h][ks] = ld_chunk<E>(table, irow, ks, kg);
+        for (int ks = 0; ks < KS; ++ks) bn[h][ks] = frag_chunk<E>(table, irow, ks, kg);
     }
-    for (; u < npairs; u += ustep) {
+    for (int u = deal.first; u < deal.ntiles; u += deal.tstep) {
         uint4 b[2][KS];
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) b[h][ks] = bn[h][ks];
-            const int irow = min(1 + min(u + ustep, npairs - 1) * 32 + h * 16 + r16, N1 - 1);
+            const int irow = deal.row(u + deal.tstep, h * 16 + r16);
 #pragma unroll
-            for (int ks = 0; ks < KS; ++ks) bn[h][ks] = ld_chunk<E>(table, irow, ks, kg);
+            for (int ks = 0; ks < KS; ++ks) bn[h][ks] = frag_chunk<E>(table, irow, ks, kg);
         }
         const int i0 = 1 + u * 32 + kg * 4;             // slot j of this lane: item i0 + 16 (j >> 2) + (j & 3)
         uint4 pa[RT];
 #pragma unroll
         for (int rt = 0; rt < RT; ++rt) {
-            f32x4_t a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};      // transposed tiles: a_h[rr] = s[row r16][item i0 + 16 h + rr]
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) { Mma<bf16_t>::mma(b[0][ks], ua[rt][ks], a0); Mma<bf16_t>::mma(b[1][ks], ua[rt][ks], a1); }
+            // transposed tiles: a_h[rr] = s[row r16][item i0 + 16 h + rr]
+            const f32x4_t a0 = score_tile<bf16_t>(b[0], ua[rt]), a1 = score_tile<bf16_t>(b[1], ua[rt]);
             float p[8];
 #pragma unroll
             for (int rr = 0; rr < 4; ++rr) {
@@ -264,46 +169,7 @@ __global__ void __launch_bounds__(256) ceb_bwd_rows_kernel(const bf16_t* __restr
             }
         }
     }
-#pragma unroll 1
-    for (int w = 0; w < 4; ++w) {
-        if (wave == w) {
-#pragma unroll
-            for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-                for (int n = 0; n < NT; ++n)
-#pragma unroll
-                    for (int rr = 0; rr < 4; ++rr) {
-                        float* o = dsh + (rt * 16 + kg * 4 + rr) * E + (n >> 1) * 32 + 2 * r16 + (n & 1);
-                        *o = w == 0 ? d[rt][n][rr] : *o + d[rt][n][rr];
-                    }
-        }
-        __syncthreads();
-    }
-    for (int e = tid; e < G * E; e += 256) {
-        const int row = r0 + e / E;
-        if (row < R) ws[((size_t)blockIdx.y * R + row) * E + (e % E)] = dsh[e];
-    }
-}
-
-// d_prec[r] = g w[r] (the ranges' partials in range order - table_b[tgt_r]); exact zeros for the rows that are not trained
-__global__ void __launch_bounds__(256) ceb_rows_finish_kernel(const float* __restrict__ ws, const bf16_t* __restrict__ table,
-                                                              const int32_t* __restrict__ tgt, const float* __restrict__ log_mask,
-                                                              const float* __restrict__ loss_ws, float loss_scale,
-                                                              const float* __restrict__ loss_scale_dev, float* __restrict__ d_prec, int R, int N1,
-                                                              int E, int gy) {
-    const float gw = ce_gw(loss_ws, loss_scale, loss_scale_dev);
-    const size_t total = (size_t)R * E;
-    for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (size_t)gridDim.x * 256) {
-        const int r = (int)(idx / E), e = (int)(idx % E);
-        const int tg = tgt[r];
-        float v = 0.f;
-        if (gw != 0.f && ce_trained(log_mask, tg, r, N1)) {
-            float s = 0.f;
-            for (int y = 0; y < gy; ++y) s += ws[(size_t)y * total + idx];
-            v = gw * (s - (float)table[(size_t)tg * E + e]);
-        }
-        d_prec[idx] = v;
-    }
+    ce_rows_partial_store<G, E>(d, dsh, ws, R, r0, [](int n, int c) { return (n >> 1) * 32 + 2 * c + (n & 1); });
 }
 
 template <int E, int IT>
@@ -323,28 +189,20 @@ __global__ void __launch_bounds__(256) ceb_bwd_items_kernel(const bf16_t* __rest
         f32x4_t d[IT][NT];
 #pragma unroll
         for (int it = 0; it < IT; ++it) {
-            const int irow = min(1 + (grp * IT + it) * 16 + r16, N1 - 1);
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) b[it][ks] = ld_chunk<E>(table, irow, ks, kg);
+            frag_load<E>(b[it], table, min(1 + (grp * IT + it) * 16 + r16, N1 - 1), kg);
 #pragma unroll
             for (int n = 0; n < NT; ++n) d[it][n] = f32x4_t{0.f, 0.f, 0.f, 0.f};
         }
         uint4 an[2][KS];
 #pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int urow = min(h * 16 + r16, R - 1);
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) an[h][ks] = ld_chunk<E>(prec, urow, ks, kg);
-        }
+        for (int h = 0; h < 2; ++h) frag_load<E>(an[h], prec, min(h * 16 + r16, R - 1), kg);
         for (int rp = 0; rp < rpairs; ++rp) {
             uint4 ua[2][KS];
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
 #pragma unroll
                 for (int ks = 0; ks < KS; ++ks) ua[h][ks] = an[h][ks];
-                const int urow = min(min(rp + 1, rpairs - 1) * 32 + h * 16 + r16, R - 1);
-#pragma unroll
-                for (int ks = 0; ks < KS; ++ks) an[h][ks] = ld_chunk<E>(prec, urow, ks, kg);
+                frag_load<E>(an[h], prec, min(min(rp + 1, rpairs - 1) * 32 + h * 16 + r16, R - 1), kg);
             }
             const int q0 = rp * 32 + kg * 4;             // slot j of this lane: row q0 + 16 (j >> 2) + (j & 3)
             int tgj[8];
@@ -371,9 +229,7 @@ __global__ void __launch_bounds__(256) ceb_bwd_items_kernel(const bf16_t* __rest
 #pragma unroll
             for (int it = 0; it < IT; ++it) {
                 const int i = 1 + (grp * IT + it) * 16 + r16;           // this lane's item column of the score tiles
-                f32x4_t a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};      // a_h[rr] = s[row q0 + 16 h + rr][item i]
-#pragma unroll
-                for (int ks = 0; ks < KS; ++ks) { Mma<bf16_t>::mma(ua[0][ks], b[it][ks], a0); Mma<bf16_t>::mma(ua[1][ks], b[it][ks], a1); }
+                const f32x4_t a0 = score_tile<bf16_t>(ua[0], b[it]), a1 = score_tile<bf16_t>(ua[1], b[it]);      // a_h[rr] = s[row q0 + 16 h + rr][item i]
                 float c[8];
 #pragma unroll
                 for (int rr = 0; rr < 4; ++rr) {
@@ -399,24 +255,8 @@ __global__ void __launch_bounds__(256) ceb_bwd_items_kernel(const bf16_t* __rest
     }
 }
 
-bool ceb_width_ok(int E) { return E == 64 || E == 128; }
-bool ceb_shape_ok(int R, int N1, int E, int ranges) { return R > 0 && N1 >= 2 && ceb_width_ok(E) && ranges >= 0 && ranges <= MAX_RANGES; }
+using WidthsBf16 = Widths<64, 128>;
 
-// the library's range count: about two workgroups per CU over the 64-row groups, at most MAX_RANGES and at most one range per 16-item tile
-int ceb_ranges(int R, int N1) {
-    const int gx = (R + G - 1) / G, ntiles = (N1 - 1 + 15) / 16;
-    int gy = (2 * a4r_cu_count() + gx - 1) / gx;
-    if (gy > MAX_RANGES) gy = MAX_RANGES;
-    if (gy > ntiles) gy = ntiles;
-    return gy < 1 ? 1 : gy;
-}
-
-template <int E> int launch_rows(hipStream_t s, dim3 grid, const bf16_t* prec, const bf16_t* table, const float* lse, float* ws, int R, int N1) {
-    const size_t lds = (size_t)G * E * sizeof(float);
-    if (int rc = a4r_set_lds(ceb_bwd_rows_kernel<E>, lds)) return rc;
-    hipLaunchKernelGGL((ceb_bwd_rows_kernel<E>), grid, dim3(256), lds, s, prec, table, lse, ws, R, N1);
-    return A4R_OK;
-}
 template <int E, int IT>
 void launch_items(hipStream_t s, int ntiles, const bf16_t* prec, const bf16_t* table, const int32_t* tgt, const float* log_mask, const float* lse,
                   const float* loss_ws, float loss_scale, const float* loss_scale_dev, float* d_table, int ldg, int R, int N1) {
@@ -426,15 +266,6 @@ void launch_items(hipStream_t s, int ntiles, const bf16_t* prec, const bf16_t* t
     hipLaunchKernelGGL((ceb_bwd_items_kernel<E, IT>), dim3(grid), dim3(256), 0, s, prec, table, tgt, log_mask, lse, loss_ws, loss_scale,
                        loss_scale_dev, d_table, ldg, R, N1);
 }
-template <int E>
-void launch_items_e(hipStream_t s, const bf16_t* prec, const bf16_t* table, const int32_t* tgt, const float* log_mask, const float* lse,
-                    const float* loss_ws, float loss_scale, const float* loss_scale_dev, float* d_table, int ldg, int R, int N1) {
-    const int ntiles = (N1 - 1 + 15) / 16;
-    if (ntiles >= ITEMS_WIDE_TILES) launch_items<E, 4>(s, ntiles, prec, table, tgt, log_mask, lse, loss_ws, loss_scale, loss_scale_dev, d_table, ldg, R, N1);
-    else launch_items<E, 1>(s, ntiles, prec, table, tgt, log_mask, lse, loss_ws, loss_scale, loss_scale_dev, d_table, ldg, R, N1);
-}
-
-bool aligned16(const void* a, const void* b) { return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15u) == 0; }
 
 }  // namespace
 
@@ -448,60 +279,67 @@ extern "C" int a4r_score_ce_bf16_cast(void* stream, const float* src, void* dst,
 
 extern "C" int a4r_score_ce_bf16_ranges(int R, int N1) {
     if (R <= 0 || N1 < 2) return A4R_EINVAL;
-    return ceb_ranges(R, N1);
+    return ce_ranges(R, N1, G);
 }
 
 extern "C" size_t a4r_score_ce_bf16_ws_bytes(int R, int N1, int E, int ranges) {
-    if (!ceb_shape_ok(R, N1, E, ranges)) return 0;
-    const int gy = ranges ? ranges : ceb_ranges(R, N1);
-    return (size_t)gy * (size_t)R * (size_t)E * sizeof(float);          // the backward's partials; the forward's triples (4 floats a row) fit in it
+    if (!ce_shape_ok(WidthsBf16{}, R, N1, E, ranges)) return 0;
+    return ce_ws_bytes(ranges ? ranges : ce_ranges(R, N1, G), R, E);
 }
 
 extern "C" int a4r_score_ce_bf16_fwd(void* stream, const void* prec_b, const void* table_b, const int32_t* tgt, const float* log_mask, float* lse,
                                      float* s_tgt, float* loss_ws, void* ws, int R, int N1, int E, int ranges) {
-    if (!prec_b || !table_b || !tgt || !log_mask || !lse || !s_tgt || !loss_ws || !ws || !ceb_shape_ok(R, N1, E, ranges)) return A4R_EINVAL;
-    if (!aligned16(prec_b, table_b) || (reinterpret_cast<uintptr_t>(ws) & 15u)) return A4R_EINVAL;
+    if (!prec_b || !table_b || !tgt || !log_mask || !lse || !s_tgt || !loss_ws || !ws) return A4R_EINVAL;
+    if (!ce_args_ok(WidthsBf16{}, prec_b, table_b, R, N1, E, ranges) || (reinterpret_cast<uintptr_t>(ws) & 15u)) return A4R_EINVAL;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const bf16_t* prec = static_cast<const bf16_t*>(prec_b);
     const bf16_t* table = static_cast<const bf16_t*>(table_b);
-    const int gy = ranges ? ranges : ceb_ranges(R, N1);
+    const int gy = ranges ? ranges : ce_ranges(R, N1, G);
     const dim3 grid((R + G - 1) / G, gy);
     float* w = static_cast<float*>(ws);
-    if (E == 64) hipLaunchKernelGGL(ceb_fwd_kernel<64>, grid, dim3(256), 0, s, prec, table, tgt, w, R, N1);
-    else hipLaunchKernelGGL(ceb_fwd_kernel<128>, grid, dim3(256), 0, s, prec, table, tgt, w, R, N1);
-    hipLaunchKernelGGL(ceb_merge_kernel, dim3(1), dim3(256), 0, s, w, tgt, log_mask, lse, s_tgt, loss_ws, R, N1, gy);
+    with_width(WidthsBf16{}, E, [&](auto e) {
+        hipLaunchKernelGGL(ceb_fwd_kernel<decltype(e)::value>, grid, dim3(256), 0, s, prec, table, tgt, w, R, N1);
+    });
+    hipLaunchKernelGGL(ce_merge_kernel, dim3(1), dim3(256), 0, s, w, tgt, log_mask, lse, s_tgt, loss_ws, R, N1, gy);
     return a4r_launch_status();
 }
 
 extern "C" int a4r_score_ce_bf16_bwd_rows(void* stream, const void* prec_b, const void* table_b, const int32_t* tgt, const float* log_mask,
                                           const float* lse, const float* loss_ws, float loss_scale, const float* loss_scale_dev, float* d_prec,
                                           void* ws, int R, int N1, int E, int ranges) {
-    if (!prec_b || !table_b || !tgt || !log_mask || !lse || !loss_ws || !d_prec || !ws || !ceb_shape_ok(R, N1, E, ranges)) return A4R_EINVAL;
-    if (!aligned16(prec_b, table_b) || (reinterpret_cast<uintptr_t>(ws) & 15u)) return A4R_EINVAL;
+    if (!prec_b || !table_b || !tgt || !log_mask || !lse || !loss_ws || !d_prec || !ws) return A4R_EINVAL;
+    if (!ce_args_ok(WidthsBf16{}, prec_b, table_b, R, N1, E, ranges) || (reinterpret_cast<uintptr_t>(ws) & 15u)) return A4R_EINVAL;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const bf16_t* prec = static_cast<const bf16_t*>(prec_b);
     const bf16_t* table = static_cast<const bf16_t*>(table_b);
-    const int gy = ranges ? ranges : ceb_ranges(R, N1);
+    const int gy = ranges ? ranges : ce_ranges(R, N1, G);
     const dim3 grid((R + G - 1) / G, gy);
     float* w = static_cast<float*>(ws);
-    const int rc = E == 64 ? launch_rows<64>(s, grid, prec, table, lse, w, R, N1) : launch_rows<128>(s, grid, prec, table, lse, w, R, N1);
+    int rc = A4R_OK;
+    with_width(WidthsBf16{}, E, [&](auto e) {
+        constexpr int W = decltype(e)::value;
+        const size_t lds = (size_t)G * W * sizeof(float);
+        if ((rc = a4r_set_lds(ceb_bwd_rows_kernel<W>, lds))) return;
+        hipLaunchKernelGGL(ceb_bwd_rows_kernel<W>, grid, dim3(256), lds, s, prec, table, lse, w, R, N1);
+    });
     if (rc) return rc;
-    const size_t total = (size_t)R * E;
-    const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-    hipLaunchKernelGGL(ceb_rows_finish_kernel, dim3(blocks), dim3(256), 0, s, w, table, tgt, log_mask, loss_ws, loss_scale, loss_scale_dev, d_prec,
-                       R, N1, E, gy);
+    launch_ce_rows_finish(s, w, table, tgt, log_mask, loss_ws, loss_scale, loss_scale_dev, d_prec, R, N1, E, gy);
     return a4r_launch_status();
 }
 
 extern "C" int a4r_score_ce_bf16_bwd_items(void* stream, const void* prec_b, const void* table_b, const int32_t* tgt, const float* log_mask,
                                            const float* lse, const float* loss_ws, float loss_scale, const float* loss_scale_dev, float* d_table,
                                            int ldg, int R, int N1, int E) {
-    if (!prec_b || !table_b || !tgt || !log_mask || !lse || !loss_ws || !d_table || !ceb_shape_ok(R, N1, E, 0) || ldg < E) return A4R_EINVAL;
-    if (!aligned16(prec_b, table_b)) return A4R_EINVAL;
+    if (!prec_b || !table_b || !tgt || !log_mask || !lse || !loss_ws || !d_table || ldg < E) return A4R_EINVAL;
+    if (!ce_args_ok(WidthsBf16{}, prec_b, table_b, R, N1, E, 0)) return A4R_EINVAL;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const bf16_t* prec = static_cast<const bf16_t*>(prec_b);
     const bf16_t* table = static_cast<const bf16_t*>(table_b);
-    if (E == 64) launch_items_e<64>(s, prec, table, tgt, log_mask, lse, loss_ws, loss_scale, loss_scale_dev, d_table, ldg, R, N1);
-    else launch_items_e<128>(s, prec, table, tgt, log_mask, lse, loss_ws, loss_scale, loss_scale_dev, d_table, ldg, R, N1);
+    const int ntiles = (N1 - 1 + 15) / 16;
+    with_width(WidthsBf16{}, E, [&](auto e) {
+        constexpr int W = decltype(e)::value;
+        if (ntiles >= ITEMS_WIDE_TILES) launch_items<W, 4>(s, ntiles, prec, table, tgt, log_mask, lse, loss_ws, loss_scale, loss_scale_dev, d_table, ldg, R, N1);
+        else launch_items<W, 1>(s, ntiles, prec, table, tgt, log_mask, lse, loss_ws, loss_scale, loss_scale_dev, d_table, ldg, R, N1);
+    });
     return a4r_launch_status();
 }

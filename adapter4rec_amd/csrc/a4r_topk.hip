@@ -1,8 +1,8 @@
 // Top-K recommendation: the K best items of every user, history excluded, without materialising the [users, items] score matrix.
 //
-// score(u, i) = <prec[u], item_emb[i]> is formed exactly as a4r_eval_rank forms it (a4r_eval.hip): 16 users per workgroup as the A operand of fp32
-// MFMA 16x16x4 tiles held in registers, the item table streamed 16 rows at a time as the B operand with the next tile's fragments requested one
-// tile ahead, the 4 waves of a workgroup taking every 4th tile of the workgroup's item range.  Same instruction sequence, same bits.
+// score(u, i) = <prec[u], item_emb[i]> comes from the item-table score sweep (a4r_score_sweep.h), fp32, 16 users per workgroup, requested one
+// tile ahead.  a4r_eval_rank forms its scores by the same fragments and the same MFMA chain (its hot loop writes them out itself, a4r_eval.hip),
+// hence the same bits: tests/test_topk_gpu.py holds the two against each other.
 //
 // Selection.  An item is a 64-bit key  orderable(score) << 32 | ~id : one unsigned compare orders by score descending, then id ascending (NaN maps
 // below -inf, -0 onto +0; key 0 is "no item").  Every user keeps a candidate buffer in LDS and a threshold, the K-th best key the workgroup
@@ -15,7 +15,7 @@
 // listed key's final position is its position in its own list plus the number of keys above it in the others (binary searches in LDS; keys are
 // unique, so positions are distinct).  Keys are a total order and each item range holds every item of the global top K that falls in it, so
 // the result does not depend on the grid.
-#include "a4r_common.h"
+#include "a4r_score_sweep.h"
 #include "../../include/a4r.h"
 
 namespace {
@@ -106,39 +106,23 @@ __global__ void __launch_bounds__(256) topk_partial_kernel(const float* __restri
         for (int m = 0; m < PER; ++m)
             if (pos[m] >= 0) excl[ul][pos[m]] = v[m];
     }
-    // A operand: 16 users x E, lane (user r16, kg) holds chunk (ks*4 + kg) -- as eval_rank_kernel
-    uint4 ua[KS];
-    const int urow = min(u0 + r16, U - 1);
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) ua[ks] = *reinterpret_cast<const uint4*>(prec + (size_t)urow * E + (ks * 4 + kg) * 4);
+    uint4 ua[KS];                                    // A operand: the 16 users
+    frag_load<E>(ua, prec, min(u0 + r16, U - 1), kg);
     __syncthreads();
-    const int ntiles = (N1 - 1 + 15) / 16, tstep = gridDim.y * 4;
-    const int first = blockIdx.y * 4;
-    const int nsteps = first < ntiles ? (ntiles - first + tstep - 1) / tstep : 0;     // the same for the 4 waves: they meet at every step's barrier
+    const SweepDeal<> deal(N1, wave);
+    const int nsteps = deal.steps();                 // the 4 waves meet at every step's barrier
     uint64_t thr[4] = {0, 0, 0, 0};
     bool live[4];
 #pragma unroll
     for (int rr = 0; rr < 4; ++rr) live[rr] = u0 + kg * 4 + rr < U;
-    int t = first + wave;
+    int t = deal.first;
     uint4 bn[KS];
-    {
-        const int irow = min(1 + min(t, ntiles - 1) * 16 + r16, N1 - 1);
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) bn[ks] = *reinterpret_cast<const uint4*>(item_emb + (size_t)irow * E + (ks * 4 + kg) * 4);
-    }
-    for (int s = 0; s < nsteps; ++s, t += tstep) {
+    sweep_begin<E, true>(bn, item_emb, deal, r16, kg);
+    for (int s = 0; s < nsteps; ++s, t += deal.tstep) {
         const int i = 1 + t * 16 + r16;                 // this lane's item column (>= N1 past the end of the table: nothing to add)
         uint4 b[KS];
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) b[ks] = bn[ks];
-        {
-            const int irow = min(1 + min(t + tstep, ntiles - 1) * 16 + r16, N1 - 1);      // (past the end: the last tile again, never used)
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) bn[ks] = *reinterpret_cast<const uint4*>(item_emb + (size_t)irow * E + (ks * 4 + kg) * 4);
-        }
-        f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) Mma<float>::mma(ua[ks], b[ks], acc);
+        sweep_next<E, true>(b, bn, item_emb, deal, t, r16, kg);
+        const f32x4_t acc = score_tile<float>(ua, b);
 #pragma unroll
         for (int rr = 0; rr < 4; ++rr) {
             const uint64_t key = topk_key(acc[rr], i);
@@ -206,10 +190,7 @@ __global__ void __launch_bounds__(256) topk_merge_kernel(const uint64_t* __restr
 }
 
 int topk_ranges(int U, int N1) {                     // a4r_eval_rank's grid, at most MAX_RANGES item ranges
-    const int gx = (U + 15) / 16;
-    int gy = 2048 / gx; if (gy < 1) gy = 1;
-    const int ntiles = (N1 - 1 + 15) / 16;
-    if (gy > (ntiles + 3) / 4) gy = (ntiles + 3) / 4;
+    const int gy = sweep_ranges(U, N1);
     return gy < MAX_RANGES ? gy : MAX_RANGES;
 }
 
@@ -217,13 +198,6 @@ int topk_cap(int K) {                                // candidate slots per user
     int c = 128;
     while (c < K + STEP_KEYS) c <<= 1;
     return c;
-}
-
-template <int E> int launch_partial(hipStream_t s, dim3 grid, size_t lds, const float* prec, const float* item_emb, const int32_t* excl_ptr,
-                                    const int32_t* excl_idx, uint64_t* ws, int U, int N1, int K, int cap) {
-    if (int rc = a4r_set_lds(topk_partial_kernel<E>, lds)) return rc;
-    hipLaunchKernelGGL(topk_partial_kernel<E>, grid, dim3(256), lds, s, prec, item_emb, excl_ptr, excl_idx, ws, U, N1, K, cap);
-    return A4R_OK;
 }
 
 bool topk_shape_ok(int U, int N1, int K) { return U > 0 && N1 >= 2 && K >= 1 && K <= A4R_TOPK_MAX_K; }
@@ -238,19 +212,19 @@ extern "C" size_t a4r_topk_ws_bytes(int U, int N1, int K) {
 extern "C" int a4r_topk_items(void* stream, const float* prec, const float* item_emb, const int32_t* excl_ptr, const int32_t* excl_idx,
                               int32_t* ids, float* scores, void* ws, int U, int N1, int E, int K) {
     if (!prec || !item_emb || !excl_ptr || !excl_idx || !ids || !scores || !ws || !topk_shape_ok(U, N1, K)) return A4R_EINVAL;
-    if (E != 64 && E != 128 && E != 256 && E != 512) return A4R_EINVAL;
-    if ((reinterpret_cast<uintptr_t>(prec) | reinterpret_cast<uintptr_t>(item_emb)) & 15u) return A4R_EINVAL;
+    if (!width_served(WidthsF32{}, E) || !aligned16(prec, item_emb)) return A4R_EINVAL;
     if (reinterpret_cast<uintptr_t>(ws) & 7u) return A4R_EINVAL;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     uint64_t* w = static_cast<uint64_t*>(ws);
     const int gy = topk_ranges(U, N1), cap = topk_cap(K);
     const dim3 grid((U + 15) / 16, gy);
     const size_t lds = (size_t)16 * cap * sizeof(uint64_t);
-    int rc;
-    if (E == 64) rc = launch_partial<64>(s, grid, lds, prec, item_emb, excl_ptr, excl_idx, w, U, N1, K, cap);
-    else if (E == 128) rc = launch_partial<128>(s, grid, lds, prec, item_emb, excl_ptr, excl_idx, w, U, N1, K, cap);
-    else if (E == 256) rc = launch_partial<256>(s, grid, lds, prec, item_emb, excl_ptr, excl_idx, w, U, N1, K, cap);
-    else rc = launch_partial<512>(s, grid, lds, prec, item_emb, excl_ptr, excl_idx, w, U, N1, K, cap);
+    int rc = A4R_OK;
+    with_width(WidthsF32{}, E, [&](auto e) {
+        const auto kernel = topk_partial_kernel<decltype(e)::value>;
+        if ((rc = a4r_set_lds(kernel, lds))) return;
+        hipLaunchKernelGGL(kernel, grid, dim3(256), lds, s, prec, item_emb, excl_ptr, excl_idx, w, U, N1, K, cap);
+    });
     if (rc) return rc;
     if (gy == 1) {
         const int64_t n = (int64_t)U * K;
