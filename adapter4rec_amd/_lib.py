@@ -194,7 +194,8 @@ def lib():
                 '(hipcc --offload-arch=gfx950).  adapter4rec_amd has no CPU / PyTorch fallback.')
         _lib = C.CDLL(LIB_PATH)
         from ._lib_ce_bf16 import SCORE_CE_BF16_SIGNATURES            # (the bf16 cross-entropy head's exports: a table of their own, bottom of this file)
-        tables = dict(SIGNATURES, **SCORE_CE_BF16_SIGNATURES)
+        from ._lib_candidates import CANDIDATES_SIGNATURES            # (eval and top-K within a candidate set: likewise)
+        tables = dict(SIGNATURES, **SCORE_CE_BF16_SIGNATURES, **CANDIDATES_SIGNATURES)
         missing = [name for name in tables if not hasattr(_lib, name)]
         if missing:                   # a build from before an entry point was added (additions keep the ABI number: no argument list changes)
             _lib = None
@@ -928,8 +929,15 @@ _CE_BF16_NAMES = ('SCORE_CE_BF16_E', 'SCORE_CE_BF16_ROWS', 'SCORE_CE_BF16_SIGNAT
                   'score_ce_bf16_ranges', 'score_ce_bf16_ws_bytes')
 
 
+# Evaluation and top-K within a candidate set of items: include/a4r_candidates.h and _lib_candidates.py, held the same way.
+_CANDIDATES_NAMES = ('CANDIDATES_SIGNATURES', 'candidate_mask', 'eval_rank_cand', 'topk_items_cand')
+
+
 def __getattr__(name):
     if name in _CE_BF16_NAMES:
         from . import _lib_ce_bf16
         return getattr(_lib_ce_bf16, name)
+    if name in _CANDIDATES_NAMES:
+        from . import _lib_candidates
+        return getattr(_lib_candidates, name)
     raise AttributeError(f'module {__name__!r} has no attribute {name!r}')

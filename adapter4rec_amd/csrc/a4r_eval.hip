@@ -15,10 +15,14 @@ namespace {
 
 constexpr int MAXH = A4R_EVAL_MAX_HISTORY;   // history ids per user kept in LDS (reference keeps <= max_seq_len + 2 = 22; the engine allows max_seq_len <= 255)
 
-template <int E>
+// CAND (a4r_eval_rank_cand, include/a4r_candidates.h): only the items i with cand[i] != 0 are counted -- one byte per table row, read from global
+// memory (cache-resident: 500 KB at 500 000 items), the byte of a wave's next tile requested with that tile's fragments.  CAND = false is the
+// kernel as it was: every `if constexpr (CAND)` below drops out of it, and cand is never read.
+template <int E, bool CAND>
 __global__ void __launch_bounds__(256) eval_rank_kernel(const float* __restrict__ prec, const float* __restrict__ item_emb,
                                                         const int32_t* __restrict__ target, const int32_t* __restrict__ hist_ptr,
-                                                        const int32_t* __restrict__ hist_idx, int32_t* __restrict__ rank, int U, int N1) {
+                                                        const int32_t* __restrict__ hist_idx, int32_t* __restrict__ rank, int U, int N1,
+                                                        const uint8_t* __restrict__ cand) {
     constexpr int KS = E / 16;                       // chunk steps (fp32: 16 k per step)
     __shared__ int32_t hist[16][MAXH];
     __shared__ int32_t nhist[16];
@@ -59,28 +63,37 @@ __global__ void __launch_bounds__(256) eval_rank_kernel(const float* __restrict_
     const int ntiles = (N1 - 1 + 15) / 16, tstep = gridDim.y * 4;
     int t = blockIdx.y * 4 + wave;
     uint4 bn[KS];
+    [[maybe_unused]] uint8_t cn = 0;                 // CAND: the candidate byte of this lane's item in the requested tile
     {
         const int irow = min(1 + min(t, ntiles - 1) * 16 + r16, N1 - 1);
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) bn[ks] = *reinterpret_cast<const uint4*>(item_emb + (size_t)irow * E + (ks * 4 + kg) * 4);
+        if constexpr (CAND) cn = cand[irow];
     }
     for (; t < ntiles; t += tstep) {
         const int i = 1 + t * 16 + r16;                 // this lane's item column
         uint4 b[KS];
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) b[ks] = bn[ks];
+        [[maybe_unused]] const uint8_t c = cn;
         {
             const int irow = min(1 + min(t + tstep, ntiles - 1) * 16 + r16, N1 - 1);      // (past the end: the last tile again, never used)
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) bn[ks] = *reinterpret_cast<const uint4*>(item_emb + (size_t)irow * E + (ks * 4 + kg) * 4);
+            if constexpr (CAND) cn = cand[irow];
         }
         f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) Mma<float>::mma(ua[ks], b[ks], acc);
         // EVERY item that beats the target is counted here; the user's history items among them are taken back below -- a scan of the (up to 264) history ids
         // per beating item was most of this loop (on random scores half the items beat the target: 36 TF/s = 0.23 of the fp32 MFMA rate, round 5)
+        if constexpr (CAND) {
 #pragma unroll
-        for (int rr = 0; rr < 4; ++rr) local[rr] += (i < N1 && acc[rr] > ts[rr]) ? 1 : 0;
+            for (int rr = 0; rr < 4; ++rr) local[rr] += (i < N1 && c != 0 && acc[rr] > ts[rr]) ? 1 : 0;
+        } else {
+#pragma unroll
+            for (int rr = 0; rr < 4; ++rr) local[rr] += (i < N1 && acc[rr] > ts[rr]) ? 1 : 0;
+        }
     }
     // The history items: score(u, h) for the j-th history id of each of the 16 users by the SAME instruction sequence (B rows = those ids, the diagonal kept, as for
     // the target: an element's bits do not depend on the column it sits in), once per id -- a repeated id, the pad item 0 or an id outside the table counts nothing,
@@ -93,6 +106,7 @@ __global__ void __launch_bounds__(256) eval_rank_kernel(const float* __restrict_
             const int h = j < nhist[r16] ? hist[r16][j] : 0;
             bool ok = h >= 1 && h < N1 && u0 + r16 < U;
             for (int k = 0; k < j && ok; ++k) ok = hist[r16][k] != h;          // first occurrence only
+            if constexpr (CAND) ok = ok && cand[h] != 0;                      // (a history id that is no candidate was never counted)
             const int hrow = ok ? h : 0;
             uint4 b[KS];
             frag_load<E>(b, item_emb, hrow, kg);
@@ -117,17 +131,29 @@ __global__ void fill_i32_kernel(int32_t* p, int n, int v) {
     for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) p[i] = v;
 }
 
-}  // namespace
-
-extern "C" int a4r_eval_rank(void* stream, const float* prec, const float* item_emb, const int32_t* target,
-                             const int32_t* hist_ptr, const int32_t* hist_idx, int32_t* rank, int U, int N1, int E) {
-    if (!prec || !item_emb || !target || !hist_ptr || !hist_idx || !rank || U <= 0 || N1 < 2) return A4R_EINVAL;
+// the one launch path of both exports; cand is read by the CAND = true kernels only
+template <bool CAND>
+int eval_rank_launch(void* stream, const float* prec, const float* item_emb, const int32_t* target, const int32_t* hist_ptr,
+                     const int32_t* hist_idx, const uint8_t* cand, int32_t* rank, int U, int N1, int E) {
+    if (!prec || !item_emb || !target || !hist_ptr || !hist_idx || !rank || (CAND && !cand) || U <= 0 || N1 < 2) return A4R_EINVAL;
     if (!width_served(WidthsF32{}, E) || !aligned16(prec, item_emb)) return A4R_EINVAL;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(fill_i32_kernel, dim3((U + 255) / 256), dim3(256), 0, s, rank, U, 1);
     const dim3 grid((U + 15) / 16, sweep_ranges(U, N1));
     with_width(WidthsF32{}, E, [&](auto e) {
-        hipLaunchKernelGGL(eval_rank_kernel<decltype(e)::value>, grid, dim3(256), 0, s, prec, item_emb, target, hist_ptr, hist_idx, rank, U, N1);
+        hipLaunchKernelGGL((eval_rank_kernel<decltype(e)::value, CAND>), grid, dim3(256), 0, s, prec, item_emb, target, hist_ptr, hist_idx, rank, U, N1, cand);
     });
     return a4r_launch_status();
+}
+
+}  // namespace
+
+extern "C" int a4r_eval_rank(void* stream, const float* prec, const float* item_emb, const int32_t* target,
+                             const int32_t* hist_ptr, const int32_t* hist_idx, int32_t* rank, int U, int N1, int E) {
+    return eval_rank_launch<false>(stream, prec, item_emb, target, hist_ptr, hist_idx, nullptr, rank, U, N1, E);
+}
+
+extern "C" int a4r_eval_rank_cand(void* stream, const float* prec, const float* item_emb, const int32_t* target,
+                                  const int32_t* hist_ptr, const int32_t* hist_idx, const uint8_t* cand, int32_t* rank, int U, int N1, int E) {
+    return eval_rank_launch<true>(stream, prec, item_emb, target, hist_ptr, hist_idx, cand, rank, U, N1, E);
 }

@@ -64,10 +64,13 @@ __device__ void topk_compact(uint64_t* buf, int cap, int K, int32_t* cnt, uint64
     __syncthreads();
 }
 
-template <int E>
+// CAND (a4r_topk_items_cand, include/a4r_candidates.h): an item is kept only if cand[i] != 0 -- a byte per table row in global memory, tested
+// beside the exclusion search, for threshold-beating items only.  CAND = false is the kernel as it was and never reads cand.
+template <int E, bool CAND>
 __global__ void __launch_bounds__(256) topk_partial_kernel(const float* __restrict__ prec, const float* __restrict__ item_emb,
                                                            const int32_t* __restrict__ excl_ptr, const int32_t* __restrict__ excl_idx,
-                                                           uint64_t* __restrict__ ws, int U, int N1, int K, int cap) {
+                                                           uint64_t* __restrict__ ws, int U, int N1, int K, int cap,
+                                                           const uint8_t* __restrict__ cand) {
     constexpr int KS = E / 16;                       // chunk steps (fp32: 16 k per step)
     constexpr int PER = (MAXX + 15) / 16;            // exclusion ids per thread while sorting
     extern __shared__ uint64_t buf[];                // [16][cap] candidate keys
@@ -127,6 +130,8 @@ __global__ void __launch_bounds__(256) topk_partial_kernel(const float* __restri
         for (int rr = 0; rr < 4; ++rr) {
             const uint64_t key = topk_key(acc[rr], i);
             if (i < N1 && live[rr] && key > thr[rr]) {
+                if constexpr (CAND)
+                    if (cand[i] == 0) continue;              // (ahead of the search: under a sparse mask the thresholds stay low for long)
                 const int ul = kg * 4 + rr;
                 int lo = 0, hi = nex[ul];
                 while (lo < hi) {
@@ -202,16 +207,11 @@ int topk_cap(int K) {                                // candidate slots per user
 
 bool topk_shape_ok(int U, int N1, int K) { return U > 0 && N1 >= 2 && K >= 1 && K <= A4R_TOPK_MAX_K; }
 
-}  // namespace
-
-extern "C" size_t a4r_topk_ws_bytes(int U, int N1, int K) {
-    if (!topk_shape_ok(U, N1, K)) return 0;
-    return (size_t)topk_ranges(U, N1) * (size_t)U * (size_t)K * sizeof(uint64_t);
-}
-
-extern "C" int a4r_topk_items(void* stream, const float* prec, const float* item_emb, const int32_t* excl_ptr, const int32_t* excl_idx,
-                              int32_t* ids, float* scores, void* ws, int U, int N1, int E, int K) {
-    if (!prec || !item_emb || !excl_ptr || !excl_idx || !ids || !scores || !ws || !topk_shape_ok(U, N1, K)) return A4R_EINVAL;
+// the one launch path of both exports; cand is read by the CAND = true kernels only, the merge and decode launches are shared
+template <bool CAND>
+int topk_launch(void* stream, const float* prec, const float* item_emb, const int32_t* excl_ptr, const int32_t* excl_idx, const uint8_t* cand,
+                int32_t* ids, float* scores, void* ws, int U, int N1, int E, int K) {
+    if (!prec || !item_emb || !excl_ptr || !excl_idx || !ids || !scores || !ws || (CAND && !cand) || !topk_shape_ok(U, N1, K)) return A4R_EINVAL;
     if (!width_served(WidthsF32{}, E) || !aligned16(prec, item_emb)) return A4R_EINVAL;
     if (reinterpret_cast<uintptr_t>(ws) & 7u) return A4R_EINVAL;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
@@ -221,9 +221,9 @@ extern "C" int a4r_topk_items(void* stream, const float* prec, const float* item
     const size_t lds = (size_t)16 * cap * sizeof(uint64_t);
     int rc = A4R_OK;
     with_width(WidthsF32{}, E, [&](auto e) {
-        const auto kernel = topk_partial_kernel<decltype(e)::value>;
+        const auto kernel = topk_partial_kernel<decltype(e)::value, CAND>;
         if ((rc = a4r_set_lds(kernel, lds))) return;
-        hipLaunchKernelGGL(kernel, grid, dim3(256), lds, s, prec, item_emb, excl_ptr, excl_idx, w, U, N1, K, cap);
+        hipLaunchKernelGGL(kernel, grid, dim3(256), lds, s, prec, item_emb, excl_ptr, excl_idx, w, U, N1, K, cap, cand);
     });
     if (rc) return rc;
     if (gy == 1) {
@@ -236,4 +236,21 @@ extern "C" int a4r_topk_items(void* stream, const float* prec, const float* item
         hipLaunchKernelGGL(topk_merge_kernel, dim3(U), dim3(256), mlds, s, w, ids, scores, U, K, gy);
     }
     return a4r_launch_status();
+}
+
+}  // namespace
+
+extern "C" size_t a4r_topk_ws_bytes(int U, int N1, int K) {
+    if (!topk_shape_ok(U, N1, K)) return 0;
+    return (size_t)topk_ranges(U, N1) * (size_t)U * (size_t)K * sizeof(uint64_t);
+}
+
+extern "C" int a4r_topk_items(void* stream, const float* prec, const float* item_emb, const int32_t* excl_ptr, const int32_t* excl_idx,
+                              int32_t* ids, float* scores, void* ws, int U, int N1, int E, int K) {
+    return topk_launch<false>(stream, prec, item_emb, excl_ptr, excl_idx, nullptr, ids, scores, ws, U, N1, E, K);
+}
+
+extern "C" int a4r_topk_items_cand(void* stream, const float* prec, const float* item_emb, const int32_t* excl_ptr, const int32_t* excl_idx,
+                                   const uint8_t* cand, int32_t* ids, float* scores, void* ws, int U, int N1, int E, int K) {
+    return topk_launch<true>(stream, prec, item_emb, excl_ptr, excl_idx, cand, ids, scores, ws, U, N1, E, K);
 }

@@ -18,7 +18,8 @@
 //   torch.ops.a4r.topk_rank_eval           a4r_eval_rank          eval_model's per-user rank                (data_utils/metrics.py:82-116)
 //   torch.ops.a4r.topk_items               a4r_topk_items         the K best items per user, list excluded  (data_utils/metrics.py: recommend); the one op that
 //                                                                 allocates: it returns (ids, scores) and takes its workspace from the caching allocator
-//   torch.ops.a4r.lora_bwd                 a4r_lora_bwd_fused     loralib Linear (query, value): every low-rank gradient in one pass (run_adapter.py:384-395)
+//   torch.ops.a4r.topk_rank_eval_cand / topk_items_cand  a4r_eval_rank_cand / a4r_topk_items_cand  the two above within a candidate set (uint8 / bool [N + 1])
+//   torch.ops.a4r.lora_bwd                 a4r_lora_bwd_fused    loralib Linear (query, value): every low-rank gradient in one pass (run_adapter.py:384-395)
 //   torch.ops.a4r.encoder_layer_fwd / _bwd a4r_encoder_layer_fwd / _bwd  one post-LN HF BertLayer + serial Houlsby wrappers per call (model/encoders.py:39-56, model/model.py:292-297)
 //   torch.ops.a4r.sasrec_block_fwd / _bwd  a4r_sasrec_block_fwd / _bwd   one adapted SASRec TransformerBlock per call (model/modules.py:45-87, model/model.py:341-376)
 //   torch.ops.a4r.embed_ln_fwd             a4r_embed_ln           HF BertEmbeddings / RobertaEmbeddings (word + position + type -> LayerNorm -> dropout)
@@ -268,6 +269,51 @@ std::tuple<Tensor, Tensor> topk_items(const Tensor& prec, const Tensor& item_emb
     return {ids, scores};
 }
 
+// a candidate set: uint8 or bool [N1] on the operands' device, one byte per table row (include/a4r_candidates.h)
+const uint8_t* chk_cand(const Tensor& cand, const char* op, const Tensor& like, int64_t N1) {
+    TORCH_CHECK(cand.defined() && (cand.scalar_type() == at::kByte || cand.scalar_type() == at::kBool), "a4r::", op, ": cand must be uint8 or bool, got ", cand.scalar_type());
+    TORCH_CHECK(cand.dim() == 1 && cand.numel() == N1 && cand.is_contiguous(), "a4r::", op, ": cand must be contiguous [N1] = [", N1, "], got ", cand.sizes());
+    TORCH_CHECK(cand.is_cuda() && cand.device() == like.device(), "a4r::", op, ": cand must be a device tensor on ", like.device(), " (no CPU path)");
+    return static_cast<const uint8_t*>(cand.data_ptr());
+}
+
+// topk_rank_eval over the items i with cand[i] != 0 (the target need not be one: include/a4r_candidates.h)
+void topk_rank_eval_cand(const Tensor& prec, const Tensor& item_emb, const Tensor& target, const Tensor& hist_ptr, const Tensor& hist_idx, const Tensor& cand, Tensor rank) {
+    TORCH_CHECK(prec.dim() == 2 && item_emb.dim() == 2 && prec.size(1) == item_emb.size(1), "a4r::topk_rank_eval_cand: prec [U, E], item_emb [N + 1, E]");
+    const int64_t U = prec.size(0), N1 = item_emb.size(0), E = prec.size(1);
+    chk_f32(prec, "prec", prec, U * E); chk_f32(item_emb, "item_emb", prec, N1 * E);
+    for (const Tensor* t : {&target, &hist_ptr, &hist_idx, (const Tensor*)&rank})
+        TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kInt && t->is_contiguous(), "a4r::topk_rank_eval_cand: target / hist_ptr / hist_idx / rank must be contiguous int32 device tensors");
+    TORCH_CHECK(target.numel() == U && rank.numel() == U && hist_ptr.numel() == U + 1, "a4r::topk_rank_eval_cand: target [U], rank [U], hist_ptr [U + 1] (CSR)");
+    const uint8_t* c = chk_cand(cand, "topk_rank_eval_cand", prec, N1);
+    status(a4r_eval_rank_cand(cur_stream(prec), prec.data_ptr<float>(), item_emb.data_ptr<float>(), target.data_ptr<int32_t>(), hist_ptr.data_ptr<int32_t>(),
+                              hist_idx.data_ptr<int32_t>(), c, rank.data_ptr<int32_t>(), (int)U, (int)N1, (int)E),
+           "a4r_eval_rank_cand");
+}
+
+// topk_items over the items i with cand[i] != 0
+std::tuple<Tensor, Tensor> topk_items_cand(const Tensor& prec, const Tensor& item_emb, const Tensor& excl_ptr, const Tensor& excl_idx, const Tensor& cand, int64_t k) {
+    TORCH_CHECK(prec.dim() == 2 && item_emb.dim() == 2 && prec.size(1) == item_emb.size(1), "a4r::topk_items_cand: prec [U, E], item_emb [N + 1, E]");
+    const int64_t U = prec.size(0), N1 = item_emb.size(0), E = prec.size(1);
+    chk_f32(prec, "prec", prec, U * E); chk_f32(item_emb, "item_emb", prec, N1 * E);
+    for (const Tensor* t : {&excl_ptr, &excl_idx})
+        TORCH_CHECK(t->is_cuda() && t->device() == prec.device() && t->scalar_type() == at::kInt && t->is_contiguous(),
+                    "a4r::topk_items_cand: excl_ptr / excl_idx must be contiguous int32 device tensors");
+    TORCH_CHECK(excl_ptr.numel() == U + 1, "a4r::topk_items_cand: excl_ptr [U + 1] (CSR)");
+    TORCH_CHECK(k >= 1 && k <= A4R_TOPK_MAX_K, "a4r::topk_items_cand: k must be in 1 .. ", A4R_TOPK_MAX_K, ", got ", k);
+    TORCH_CHECK(U >= 1 && N1 >= 2, "a4r::topk_items_cand: U >= 1 users and N1 >= 2 table rows");
+    const uint8_t* c = chk_cand(cand, "topk_items_cand", prec, N1);
+    Tensor ids = at::empty({U, k}, prec.options().dtype(at::kInt));
+    Tensor scores = at::empty({U, k}, prec.options());
+    const size_t wsb = a4r_topk_ws_bytes((int)U, (int)N1, (int)k);
+    Tensor ws = at::empty({(int64_t)wsb}, prec.options().dtype(at::kByte));
+    Tensor idx = excl_idx.numel() ? excl_idx : at::zeros({1}, excl_idx.options());     // (an empty list has no data pointer)
+    status(a4r_topk_items_cand(cur_stream(prec), prec.data_ptr<float>(), item_emb.data_ptr<float>(), excl_ptr.data_ptr<int32_t>(), idx.data_ptr<int32_t>(), c,
+                               ids.data_ptr<int32_t>(), scores.data_ptr<float>(), ws.data_ptr(), (int)U, (int)N1, (int)E, (int)k),
+           "a4r_topk_items_cand");
+    return {ids, scores};
+}
+
 // The low-rank gradients of a block's two LoRAs (query: a, value: b) from one pass over x [M, H] and the two slices dqa, dqb [M, H] of the fused qkv
 // gradient.  Aa, Ab, BTa (= B_a^T), BTb: [R, H] views (R = 8: ranks <= 8, or 16: ranks <= 15; rows past the rank zero); dAa, dAb [R, H] and dBa, dBb
 // [H, >= R] fp32, ACCUMULATED into (dB without the LoRA scaling); dbias_a / dbias_b: optional strided fp32 vectors += column sums of dqa / dqb.
@@ -500,6 +546,8 @@ TORCH_LIBRARY(a4r, m) {
           "Tensor(e!)? norm_out=None) -> ()", &fused_adamw_step);
     m.def("topk_rank_eval(Tensor prec, Tensor item_emb, Tensor target, Tensor hist_ptr, Tensor hist_idx, Tensor(a!) rank) -> ()", &topk_rank_eval);
     m.def("topk_items(Tensor prec, Tensor item_emb, Tensor excl_ptr, Tensor excl_idx, int k) -> (Tensor, Tensor)", &topk_items);
+    m.def("topk_rank_eval_cand(Tensor prec, Tensor item_emb, Tensor target, Tensor hist_ptr, Tensor hist_idx, Tensor cand, Tensor(a!) rank) -> ()", &topk_rank_eval_cand);
+    m.def("topk_items_cand(Tensor prec, Tensor item_emb, Tensor excl_ptr, Tensor excl_idx, Tensor cand, int k) -> (Tensor, Tensor)", &topk_items_cand);
     m.def("lora_bwd(Tensor x, Tensor dqa, Tensor dqb, Tensor Aa, Tensor Ab, Tensor BTa, Tensor BTb, float scale_a, float scale_b, Tensor(a!) dAa, Tensor(b!) dAb, "
           "Tensor(c!) dBa, Tensor(d!) dBb, Tensor(e!)? dbias_a, Tensor(f!)? dbias_b, Tensor(g!) ws) -> ()", &lora_bwd);
     m.def("encoder_layer_fwd(Tensor x, Tensor[] w, Tensor[] ad1, Tensor[] ad2, Tensor[] saved, Tensor(a!) x1, Tensor(b!) x_out, Tensor? key_mask, Tensor? offsets, int n_items, int S, "

@@ -123,11 +123,77 @@ def _prepare_eval_set(eval_seq, user_history, Lm, dev):
     return prep
 
 
-def eval_ranks(model, user_history, eval_seq, item_embeddings, test_batch_size, args, user_ids):
-    """Rank (1 = best) of each listed user's held-out target among all items not in the user's history."""
+def candidate_mask(candidates, n1, dev):
+    """A candidate set as a4r_eval_rank_cand / a4r_topk_items_cand read it: ``candidates`` (a bool or uint8 tensor, or an array, of N + 1 = n1
+    entries; item i is a candidate iff entry i is non-zero, entry 0 -- the pad item -- is ignored) -> a uint8 tensor [n1] on ``dev``, uploaded
+    here, once per call of the functions below.  None stays None (no restriction).  A wrong length, or no candidate among 1 .. N, raises
+    ValueError."""
+    if candidates is None:
+        return None
+    if isinstance(candidates, torch.Tensor):
+        if candidates.dtype not in (torch.bool, torch.uint8):
+            raise ValueError(f'candidates: a bool or uint8 tensor expected, got {candidates.dtype}')
+        m = candidates
+    else:
+        m = torch.from_numpy(np.ascontiguousarray(np.asarray(candidates) != 0))
+    if m.dim() != 1 or m.numel() != n1:
+        raise ValueError(f'candidates: one entry per table row expected, [{n1}] (N + 1, entry 0 = the pad item), got {tuple(m.shape)}')
+    if not bool((m[1:] != 0).any()):
+        raise ValueError('candidates: no candidate among the items 1 .. N')
+    m = m.to(dev).contiguous()
+    return m.view(torch.uint8) if m.dtype == torch.bool else m
+
+
+def read_candidates(path, item_names):
+    """A candidate file -> bool array [N + 1]: one item name per line, the names --mode recommend writes (``item_names[i]`` = the item file's
+    name of item i, [0] = the pad item: preprocess.read_behavior_names).  Blank lines and repeats are ignored; names that are no item raise
+    ValueError listing the first few."""
+    index = {name: i for i, name in enumerate(item_names) if i > 0 and name is not None}
+    mask = np.zeros(len(item_names), dtype=bool)
+    unknown = []
+    with open(path) as f:
+        for line in f:
+            name = line.strip()
+            if not name:
+                continue
+            i = index.get(name)
+            if i is None:
+                if name not in unknown:
+                    unknown.append(name)
+            else:
+                mask[i] = True
+    if unknown:
+        raise ValueError(f'{path}: {len(unknown)} name(s) that are no item of this dataset: ' + ', '.join(unknown[:5]) + (' ...' if len(unknown) > 5 else ''))
+    return mask
+
+
+def check_candidate_flag(args):
+    """--candidate_items restricts --mode test and --mode recommend; training and its per-epoch evaluation are not restricted by it, so any
+    other mode refuses the flag instead of ignoring it."""
+    if getattr(args, 'candidate_items', None) and not ('test' in args.mode or args.mode == 'recommend'):
+        raise ValueError(f'--candidate_items is honoured by --mode test and --mode recommend only, not by --mode {args.mode} '
+                         '(training and its per-epoch evaluation range over the whole catalogue)')
+
+
+def candidates_from_args(args, behaviors_path, name2id, Log_file):
+    """The runners' --candidate_items FILE -> bool array [item_num + 1] in the numbering read_behaviors gives the items, or None without the
+    flag."""
+    if not getattr(args, 'candidate_items', None):
+        return None
+    from .preprocess import read_behavior_names
+    _, item_names = read_behavior_names(behaviors_path, name2id, args.max_seq_len, args.min_seq_len)
+    mask = read_candidates(args.candidate_items, item_names)
+    Log_file.info(f'candidate items: {int(mask.sum())} of {len(item_names) - 1} from {args.candidate_items}')
+    return mask
+
+
+def eval_ranks(model, user_history, eval_seq, item_embeddings, test_batch_size, args, user_ids, candidates=None):
+    """Rank (1 = best) of each listed user's held-out target among all items not in the user's history.  ``candidates`` (candidate_mask's
+    input): among the candidate items only -- for every listed user; a target that is no candidate gets the rank it would have if it were."""
     inner = _inner(model, args)
     dev = next(model.parameters()).device
     emb = item_embeddings.to(dev).float().contiguous()
+    cand = candidate_mask(candidates, emb.shape[0], dev)
     Lm = args.max_seq_len + 1
     E = emb.shape[1]
     if len(user_ids) == 0:
@@ -158,7 +224,10 @@ def eval_ranks(model, user_history, eval_seq, item_embeddings, test_batch_size, 
                 ptr = (P['hptr'][a:b + 1] - h0).to(torch.int32)
                 hist = P['hflat32'][h0:h1 + 1]                 # (+ 1: the kernel's table is never empty; the store ends in one spare 0)
                 rank = torch.zeros(nb, dtype=torch.int32, device=dev)
-                L.eval_rank(prec, emb, P['target32'][a:b], ptr, hist, rank)
+                if cand is None:
+                    L.eval_rank(prec, emb, P['target32'][a:b], ptr, hist, rank)
+                else:
+                    L.eval_rank_cand(prec, emb, P['target32'][a:b], ptr, hist, cand, rank)
                 ranks.append(rank)
     out = torch.cat(ranks)
     if not first.all():
@@ -166,8 +235,12 @@ def eval_ranks(model, user_history, eval_seq, item_embeddings, test_batch_size, 
     return out
 
 
-def eval_model(model, user_history, eval_seq, item_embeddings, test_batch_size, args, item_num, Log_file, v_or_t, local_rank):
-    """metrics.py:82-116.  Returns mean Hit@10 over all users (ranks are gathered over the data-parallel group)."""
+def eval_model(model, user_history, eval_seq, item_embeddings, test_batch_size, args, item_num, Log_file, v_or_t, local_rank, candidates=None):
+    """metrics.py:82-116.  Returns mean Hit@10 over all users (ranks are gathered over the data-parallel group).  ``candidates``
+    (candidate_mask's input): every target is ranked among the candidate items only, and the means run over the users whose target is a
+    candidate (cold-start and split evaluation); ValueError when there is no such user."""
+    if candidates is not None:
+        return _eval_model_candidates(model, user_history, eval_seq, item_embeddings, test_batch_size, args, Log_file, v_or_t, candidates)
     world = dist.get_world_size() if dist.is_initialized() else 1
     rank_id = dist.get_rank() if dist.is_initialized() else 0
     n_users = len(eval_seq)
@@ -187,6 +260,39 @@ def eval_model(model, user_history, eval_seq, item_embeddings, test_batch_size, 
         hit, ndcg = torch.cat(parts_h), torch.cat(parts_n)
     mean_eval = [float(hit[:n_users].mean().item()), float(ndcg[:n_users].mean().item())]
     print_metrics(mean_eval, Log_file, v_or_t)
+    return mean_eval[0]
+
+
+def _eval_model_candidates(model, user_history, eval_seq, item_embeddings, test_batch_size, args, Log_file, v_or_t, candidates):
+    """eval_model within a candidate set: the same sharding, log lines and gather, with a validity flag (the user's target is a candidate)
+    travelling beside hit and ndcg; the means are sums over the valid users divided by their number."""
+    world = dist.get_world_size() if dist.is_initialized() else 1
+    rank_id = dist.get_rank() if dist.is_initialized() else 0
+    n_users = len(eval_seq)
+    sampler = SequentialDistributedSampler(range(n_users), test_batch_size, rank=rank_id, num_replicas=world)
+    user_ids = sampler.indices()
+    model.eval()
+    topK = 10
+    dev = next(model.parameters()).device
+    cand = candidate_mask(candidates, item_embeddings.shape[0], dev)          # uploaded once; eval_ranks takes it as it is
+    Log_file.info(v_or_t + '_methods   {}'.format('\t'.join(['Hit{}'.format(topK), 'nDCG{}'.format(topK)])))
+    ranks = eval_ranks(model, user_history, eval_seq, item_embeddings, test_batch_size, args, user_ids, candidates=cand).float()
+    P = _prepare_eval_set(eval_seq, user_history, args.max_seq_len + 1, dev)
+    uid = torch.from_numpy(np.asarray(user_ids, dtype=np.int64)).to(dev)
+    valid = (cand[P['target'][uid]] != 0).float() if uid.numel() else torch.zeros(0, device=dev)
+    hit = (ranks <= topK).float() * valid
+    ndcg = torch.where(ranks <= topK, 1.0 / torch.log2(ranks + 1.0), torch.zeros_like(ranks)) * valid
+    if world > 1:
+        parts = [[torch.zeros_like(t) for _ in range(world)] for t in (hit, ndcg, valid)]
+        for p, t in zip(parts, (hit, ndcg, valid)):
+            dist.all_gather(p, t)
+        hit, ndcg, valid = (torch.cat(p) for p in parts)
+    k = int(valid[:n_users].sum().item())
+    if k == 0:
+        raise ValueError(f'{v_or_t}: no user of {n_users} has a target among the candidate items')
+    mean_eval = [float(hit[:n_users].sum().item()) / k, float(ndcg[:n_users].sum().item()) / k]
+    print_metrics(mean_eval, Log_file, v_or_t)
+    Log_file.info(v_or_t + '_candidates   {} of {} users'.format(k, n_users))
     return mean_eval[0]
 
 
@@ -218,7 +324,7 @@ def _recommend_inputs(user_seqs, exclude, uids, T):
     return ids, mask, ptr, flat
 
 
-def recommend(model, user_seqs, item_embeddings, k, args, exclude=None, user_ids=None):
+def recommend(model, user_seqs, item_embeddings, k, args, exclude=None, user_ids=None, candidates=None):
     """The k best items for each listed user (default: every user of ``user_seqs``), after the user's sequence.
 
     ``user_seqs[u]``: the user's item ids (1 .. N); its last ``max_seq_len`` items go through ``user_encoder``, left-padded as an evaluation
@@ -227,13 +333,15 @@ def recommend(model, user_seqs, item_embeddings, k, args, exclude=None, user_ids
     ``get_item_embeddings`` / ``get_itemLMDB_embeddings`` / ``get_itemId_embeddings``.
     Returns (ids LongTensor [U, k], scores fp32 [U, k]) on the model's device: score descending, ties by smaller id; a user with fewer than k
     candidates gets id 0 / score -inf in the remaining slots.  One a4r_topk_items launch pair per batch of users (the [users, items] score matrix
-    is never formed)."""
+    is never formed).  ``candidates`` (candidate_mask's input: bool / uint8 [N + 1], one set for all users): the lists are drawn from the
+    candidate items only (a4r_topk_items_cand) -- the catalogue in stock, say, which no 264-id exclusion list could express."""
     inner = _inner(model, args)
     dev = next(model.parameters()).device
     emb = item_embeddings.to(dev).float().contiguous()
     T = int(args.max_seq_len)
     E = emb.shape[1]
     k = int(k)
+    cand = candidate_mask(candidates, emb.shape[0], dev)
     uids = np.arange(len(user_seqs), dtype=np.int64) if user_ids is None else np.asarray(user_ids, dtype=np.int64).reshape(-1)
     if uids.size == 0:
         return torch.zeros(0, k, dtype=torch.long, device=dev), torch.zeros(0, k, dtype=torch.float32, device=dev)
@@ -253,17 +361,21 @@ def recommend(model, user_seqs, item_embeddings, k, args, exclude=None, user_ids
             ptr = torch.from_numpy((ptr_np[a:b + 1] - h0).astype(np.int32)).to(dev)
             ids = torch.empty(nb, k, dtype=torch.int32, device=dev)
             scores = torch.empty(nb, k, dtype=torch.float32, device=dev)
-            L.topk_items(prec, emb, ptr, flat[h0:h1 + 1], k, ids, scores)
+            if cand is None:
+                L.topk_items(prec, emb, ptr, flat[h0:h1 + 1], k, ids, scores)
+            else:
+                L.topk_items_cand(prec, emb, ptr, flat[h0:h1 + 1], cand, k, ids, scores)
             out_ids.append(ids.long())
             out_scores.append(scores)
     return torch.cat(out_ids), torch.cat(out_scores)
 
 
-def write_recommendations(model, user_seqs, user_history, item_embeddings, k, batch_size, args, user_names, item_names, path):
+def write_recommendations(model, user_seqs, user_history, item_embeddings, k, batch_size, args, user_names, item_names, path, candidates=None):
     """The runners' --mode recommend: the k next items after every user's whole known sequence (``user_seqs[u]``, the evaluation input of the
     test split, whose last item is the held-out one), excluding ``user_history[u]`` plus that last item -- everything the user is known to have
     seen.  Users are sharded over the data-parallel ranks as eval_model shards them; rank 0 writes ``path``: one line per user, in uid order,
-    ``user_name \\t item_1 ... item_k \\t score_1 ... score_k`` with the item file's names (pad slots of a short list omitted)."""
+    ``user_name \\t item_1 ... item_k \\t score_1 ... score_k`` with the item file's names (pad slots of a short list omitted).
+    ``candidates``: as recommend's."""
     world = dist.get_world_size() if dist.is_initialized() else 1
     rank_id = dist.get_rank() if dist.is_initialized() else 0
     n_users = len(user_seqs)
@@ -273,7 +385,7 @@ def write_recommendations(model, user_seqs, user_history, item_embeddings, k, ba
         u = int(u)
         if u not in exclude:
             exclude[u] = np.concatenate([np.asarray(user_history[u], dtype=np.int64).reshape(-1), np.asarray(user_seqs[u][-1:], dtype=np.int64)])
-    ids, scores = recommend(model, user_seqs, item_embeddings, k, args, exclude=exclude, user_ids=uids)
+    ids, scores = recommend(model, user_seqs, item_embeddings, k, args, exclude=exclude, user_ids=uids, candidates=candidates)
     if world > 1:
         parts_i = [torch.zeros_like(ids) for _ in range(world)]
         parts_s = [torch.zeros_like(scores) for _ in range(world)]

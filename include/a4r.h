@@ -532,6 +532,10 @@ int a4r_score_ce_bwd_items(void* stream, const float* prec, const float* table, 
  * header's prototypes (adapter4rec_amd/_lib.py: SIGNATURES) and what is held against it stay as they are; adapter4rec_amd/_lib_ce_bf16.py binds them. */
 #include "a4r_score_ce_bf16.h"
 
+/* a4r_eval_rank and a4r_topk_items restricted to a candidate set of items shared by all users of a call (a4r_eval_rank_cand, a4r_topk_items_cand):
+ * a header of their own for the same reason, bound by adapter4rec_amd/_lib_candidates.py. */
+#include "a4r_candidates.h"
+
 /* The learned item-ID table of the IDRec baseline (ABI 410; Downstream/CV/model/model.py: nn.Embedding(item_num + 1, E, padding_idx=0), fed the flat
  * slot ids of a batch).  a4r_id_index, once per step: rows[i] = ids[i] when 0 <= ids[i] <= item_num, else 0 and counted in *err (overwritten: the
  * number of such slots in this call) -- rows is what a4r_rows_idx_copy gathers the table with.  The inverted index in CSR form: *n_uniq distinct

@@ -1,7 +1,9 @@
 #!/usr/bin/env python
 """Throughput of the native evaluation (reference: Downstream/Text/data_utils/metrics.py:62-116).
 
-  python tools/eval_bench.py [--items 65536] [--users 32768] [--json out.json]
+  python tools/eval_bench.py [--items 65536] [--users 32768] [--json out.json] [--candidates FRACTION]
+
+--candidates FRACTION runs the candidate-set leg instead (candidates_leg): a4r_eval_rank_cand beside a4r_eval_rank, kernels only.
 
 Times, on one MI355X, with BERT-base + Houlsby weights (random init, as bench.py):
   * the item sweep `get_item_embeddings` (all N + 1 titles through the item encoder, forward only) in the eval dtypes
@@ -33,14 +35,54 @@ def timed(fn, reps=1):
     return (time.perf_counter() - t0) / reps, out
 
 
+def candidates_leg(a, dev):
+    """--candidates FRACTION: the rank kernel alone on a random [items + 1, 64] table -- a4r_eval_rank_cand under a random candidate set of that
+    fraction of the items beside a4r_eval_rank on the same data, interleaved over two rounds (no encoder: the set concerns the rank kernel only)."""
+    from adapter4rec_amd import _lib as L
+    E, N1 = 64, a.items + 1
+    g = torch.Generator(device=dev).manual_seed(B.SEED)
+    emb = torch.randn(N1, E, device=dev, generator=g)
+    cand = (torch.rand(N1, device=dev, generator=g) < a.candidates).to(torch.uint8).contiguous()
+    res = dict(items=N1, E=E, fraction=a.candidates, candidates=int(cand[1:].ne(0).sum()))
+    for U in (512, 4096, 32768):
+        prec = torch.randn(U, E, device=dev, generator=g)
+        target = torch.randint(1, N1, (U,), device=dev, dtype=torch.int32, generator=g)
+        ptr = torch.arange(0, U + 1, device=dev, dtype=torch.int32) * 20
+        hidx = torch.randint(1, N1, (U * 20 + 1,), device=dev, dtype=torch.int32, generator=g)
+        rank = torch.zeros(U, dtype=torch.int32, device=dev)
+        legs = dict(eval_rank=lambda: L.eval_rank(prec, emb, target, ptr, hidx, rank),
+                    eval_rank_cand=lambda: L.eval_rank_cand(prec, emb, target, ptr, hidx, cand, rank))
+        us = {n: [] for n in legs}
+        for _ in range(2):
+            for n, fn in legs.items():
+                for _ in range(2):
+                    fn()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(10):
+                    fn()
+                e1.record()
+                torch.cuda.synchronize()
+                us[n].append(round(e0.elapsed_time(e1) / 10 * 1e3, 1))
+        res[f'U{U}'] = dict(eval_rank_us=us['eval_rank'], eval_rank_cand_us=us['eval_rank_cand'],
+                            cand_over_plain=round(min(us['eval_rank_cand']) / min(us['eval_rank']), 3))
+    print(json.dumps(res, indent=1))
+    if a.json:
+        json.dump(res, open(a.json, 'w'), indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--items', type=int, default=65536)
     ap.add_argument('--users', type=int, default=32768)
     ap.add_argument('--json', default='')
+    ap.add_argument('--candidates', type=float, default=None, metavar='FRACTION',
+                    help='run the candidate-set leg instead: a4r_eval_rank_cand beside a4r_eval_rank under a random mask of this fraction')
     a = ap.parse_args()
     dev = torch.device('cuda', 0)
     torch.cuda.set_device(0)
+    if a.candidates is not None:
+        return candidates_leg(a, dev)
     from adapter4rec_amd import _lib as L
     from adapter4rec_amd.data_utils import eval_model, get_item_embeddings
     args = B.make_args(32, 'bf16')

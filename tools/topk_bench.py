@@ -2,7 +2,9 @@
 """Top-K recommendation on one MI355X: a4r_topk_items beside a4r_eval_rank (the same scoring sweep, one rank per user) and beside the torch path a
 user would otherwise write (chunked fp32 matmul, history masked, torch.topk), and recommend() end to end -- one JSON line per configuration.
 
-    python tools/topk_bench.py [--iters N] [--only NAME]
+    python tools/topk_bench.py [--iters N] [--only NAME] [--candidates FRACTION]
+
+--candidates FRACTION runs the candidate-set leg instead (cand_cfg): a4r_topk_items_cand / a4r_eval_rank_cand beside the unmasked entries, interleaved.
 
 Shapes: 32 768 users x 65 537 items (the evaluation benchmark's shape) and x 500 001 items (the ID tower's 500 000-item table), E = 64, K 10 / 100,
 histories of 20 uniform ids.  Kernel times are HIP-event means over N launches after a warm-up; per-kernel times: run this under
@@ -73,6 +75,28 @@ def kernel_cfg(name, U, N1, E, k, iters, H=20):
                 id_agreement_with_torch=round(agree, 6))
 
 
+def cand_cfg(name, U, N1, E, k, fraction, iters, rounds=2, H=20):
+    """--candidates FRACTION: a4r_topk_items_cand and a4r_eval_rank_cand under a random candidate set of that fraction of the items (1.0: every
+    item) beside the unmasked entries on the same data, the four legs interleaved `rounds` times; every round's mean is reported."""
+    from adapter4rec_amd import _lib as L
+    emb, prec, hist, ptr, tgt = data(U, N1, E, H)
+    flat = hist.reshape(-1).contiguous()
+    g = torch.Generator(device=DEV).manual_seed(1)
+    cand = (torch.rand(N1, device=DEV, generator=g) < fraction).to(torch.uint8).contiguous()
+    ids = torch.empty(U, k, dtype=torch.int32, device=DEV)
+    sc = torch.empty(U, k, dtype=torch.float32, device=DEV)
+    rank = torch.zeros(U, dtype=torch.int32, device=DEV)
+    legs = dict(topk=lambda: L.topk_items(prec, emb, ptr, flat, k, ids, sc), topk_cand=lambda: L.topk_items_cand(prec, emb, ptr, flat, cand, k, ids, sc),
+                eval_rank=lambda: L.eval_rank(prec, emb, tgt, ptr, flat, rank), eval_rank_cand=lambda: L.eval_rank_cand(prec, emb, tgt, ptr, flat, cand, rank))
+    ms = {n: [] for n in legs}
+    for _ in range(rounds):
+        for n, fn in legs.items():
+            ms[n].append(round(timed(fn, iters), 4))
+    return dict(name=name, users=U, items=N1, E=E, k=k, fraction=fraction, candidates=int(cand[1:].ne(0).sum()), rounds=rounds, iters=iters,
+                **{n + '_ms': v for n, v in ms.items()}, topk_cand_over_topk=round(min(ms['topk_cand']) / min(ms['topk']), 3),
+                eval_rank_cand_over_eval_rank=round(min(ms['eval_rank_cand']) / min(ms['eval_rank']), 3))
+
+
 def recommend_cfg(name, U, item_num, k, iters, T=20):
     from adapter4rec_amd.cv import Model
     from adapter4rec_amd.cv.data_utils import get_itemId_embeddings
@@ -97,7 +121,14 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--iters', type=int, default=20)
     ap.add_argument('--only', default=None)
+    ap.add_argument('--candidates', type=float, default=None, metavar='FRACTION',
+                    help='run the candidate-set leg instead: the masked entries beside the unmasked ones under a random mask of this fraction')
     a = ap.parse_args()
+    if a.candidates is not None:
+        for name, N1, it in (('cand_k10_65537', 65537, a.iters), ('cand_k10_500000', 500000, max(1, a.iters // 4))):
+            if not a.only or a.only == name:
+                print(json.dumps(cand_cfg(name, 32768, N1, 64, 10, a.candidates, it)), flush=True)
+        return
     cfgs = [
         ('k10_65537', lambda: kernel_cfg('k10_65537', 32768, 65537, 64, 10, a.iters)),
         ('k100_65537', lambda: kernel_cfg('k100_65537', 32768, 65537, 64, 100, a.iters)),
