@@ -195,7 +195,8 @@ def lib():
         _lib = C.CDLL(LIB_PATH)
         from ._lib_ce_bf16 import SCORE_CE_BF16_SIGNATURES            # (the bf16 cross-entropy head's exports: a table of their own, bottom of this file)
         from ._lib_candidates import CANDIDATES_SIGNATURES            # (eval and top-K within a candidate set: likewise)
-        tables = dict(SIGNATURES, **SCORE_CE_BF16_SIGNATURES, **CANDIDATES_SIGNATURES)
+        from ._lib_user_lists import USER_LISTS_SIGNATURES            # (top-K and rank within a list of each user's own: likewise)
+        tables = dict(SIGNATURES, **SCORE_CE_BF16_SIGNATURES, **CANDIDATES_SIGNATURES, **USER_LISTS_SIGNATURES)
         missing = [name for name in tables if not hasattr(_lib, name)]
         if missing:                   # a build from before an entry point was added (additions keep the ABI number: no argument list changes)
             _lib = None
@@ -933,6 +934,10 @@ _CE_BF16_NAMES = ('SCORE_CE_BF16_E', 'SCORE_CE_BF16_ROWS', 'SCORE_CE_BF16_SIGNAT
 _CANDIDATES_NAMES = ('CANDIDATES_SIGNATURES', 'candidate_mask', 'eval_rank_cand', 'topk_items_cand')
 
 
+# Top-K and rank within a candidate list of each user's own: include/a4r_user_lists.h and _lib_user_lists.py, held the same way.
+_USER_LISTS_NAMES = ('USER_LISTS_SIGNATURES', 'LIST_MAX', 'topk_lists', 'eval_rank_lists')
+
+
 def __getattr__(name):
     if name in _CE_BF16_NAMES:
         from . import _lib_ce_bf16
@@ -940,4 +945,7 @@ def __getattr__(name):
     if name in _CANDIDATES_NAMES:
         from . import _lib_candidates
         return getattr(_lib_candidates, name)
+    if name in _USER_LISTS_NAMES:
+        from . import _lib_user_lists
+        return getattr(_lib_user_lists, name)
     raise AttributeError(f'module {__name__!r} has no attribute {name!r}')

@@ -16,6 +16,7 @@
 // unique, so positions are distinct).  Keys are a total order and each item range holds every item of the global top K that falls in it, so
 // the result does not depend on the grid.
 #include "a4r_score_sweep.h"
+#include "a4r_topk_key.h"
 #include "../../include/a4r.h"
 
 namespace {
@@ -24,20 +25,7 @@ constexpr int MAXX = A4R_EVAL_MAX_HISTORY;   // exclusion ids per user kept in L
 constexpr int STEP_KEYS = 64;                // keys a step can add per user: 4 waves x 16 item columns
 constexpr int MAX_RANGES = 32;               // item ranges per user: the merge holds gy x K <= 32 x 256 keys (64 KiB) in LDS
 
-__device__ __forceinline__ uint64_t topk_key(float s, int id) {
-    uint32_t b = __float_as_uint(s);
-    if (b == 0x80000000u) b = 0u;                                           // -0 == +0: one key
-    uint32_t o = (b & 0x80000000u) ? ~b : (b | 0x80000000u);              // monotone in the float value
-    if (s != s) o = 0u;                                                     // NaN: below -inf
-    return ((uint64_t)o << 32) | (uint32_t)~(uint32_t)id;
-}
-
-__device__ __forceinline__ void topk_emit(uint64_t key, int32_t* id, float* score) {
-    if (key == 0) { *id = 0; *score = -__builtin_huge_valf(); return; }    // short list: pad slot
-    const uint32_t o = (uint32_t)(key >> 32);
-    *id = (int32_t)~(uint32_t)key;
-    *score = o == 0 ? __builtin_nanf("") : __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
-}
+// topk_key / topk_emit: a4r_topk_key.h (shared with a4r_lists.hip)
 
 // Sort each of the 16 buffers (cap keys, cap a power of two) descending, entries past the count as 0; keep the best K, reset the thresholds.
 __device__ void topk_compact(uint64_t* buf, int cap, int K, int32_t* cnt, uint64_t* thr) {

@@ -23,7 +23,8 @@ from ..inject import freeze_all
 from ..optim import from_args as optimizer_from_args
 from . import Model, ModelCPC, ViTForImageClassification, ViTMAEModel
 from .data_utils import eval_model, get_itemId_embeddings, get_itemLMDB_embeddings, open_image_db, read_behaviors, read_images
-from ..data_utils.metrics import candidate_mask, candidates_from_args, check_candidate_flag, read_candidates, write_recommendations
+from ..data_utils.metrics import (candidate_lists_from_args, candidate_mask, candidates_from_args, check_candidate_flag, read_candidate_lists, read_candidates,
+                                  write_recommendations)
 from ..data_utils.preprocess import read_behavior_names
 from .image_io import Build_Lmdb_Dataset, assemble_batch, collate_host
 from .inject import inject_adapters, optimizer_groups
@@ -100,7 +101,7 @@ def build_model(args, item_num, use_modal, cv_model, local_rank, Log_file, model
     return model.to(local_rank), start_epoch, ckpt2
 
 
-def run_eval_once(model, db, item_id_to_keys, user_history, users_eval, batch_size, item_num, mode, local_rank, args, Log_file, candidates=None):
+def run_eval_once(model, db, item_id_to_keys, user_history, users_eval, batch_size, item_num, mode, local_rank, args, Log_file, candidates=None, candidate_lists=None):
     t0 = time.time()
     Log_file.info('Validating...')
     if db is None:                                                     # --item_tower id: the table itself (run_adapter.py:275-279)
@@ -108,6 +109,8 @@ def run_eval_once(model, db, item_id_to_keys, user_history, users_eval, batch_si
     else:
         emb = get_itemLMDB_embeddings(model, item_num, item_id_to_keys, batch_size, args, local_rank, db=db)
     kw = {} if candidates is None else dict(candidates=candidates)      # --candidate_items: ranked among, and averaged over targets within, the candidate set
+    if candidate_lists is not None:                                     # --candidate_lists: ranked within the user's own list, averaged over the users who have one
+        kw = dict(candidate_lists=candidate_lists)
     hit10 = eval_model(model, user_history, users_eval, emb, batch_size, args, item_num, Log_file, mode, local_rank, **kw)
     report_time_eval(t0, Log_file)
     return hit10
@@ -242,6 +245,9 @@ def test(args, use_modal, local_rank, Log_file, Log_screen, model_dir, start_tim
     cand = candidates_from_args(args, os.path.join(args.root_data_dir, args.dataset, args.behaviors), before_name2id, Log_file)
     # --candidate_items: the mask is uploaded once, for both splits; without the flag the calls are the ones made before
     kw = {} if cand is None else dict(candidates=candidate_mask(cand, item_num + 1, next(model.parameters()).device))
+    lists = candidate_lists_from_args(args, os.path.join(args.root_data_dir, args.dataset, args.behaviors), before_name2id, Log_file)
+    if lists is not None:                                              # --candidate_lists (never beside --candidate_items: main refuses the pair)
+        kw = dict(candidate_lists=lists)
     run_eval_once(model, db, item_id_to_keys, hist_valid, users_valid, 256, item_num, 'valid', local_rank, args, Log_file, **kw)
     run_eval_once(model, db, item_id_to_keys, hist_test, users_test, 256, item_num, 'test', local_rank, args, Log_file, **kw)
 
@@ -265,7 +271,8 @@ def recommend(args, use_modal, local_rank, Log_file, Log_screen, model_dir, star
         emb = get_itemLMDB_embeddings(model, item_num, item_id_to_keys, 256, args, local_rank, db=db)
     out = args.recommend_out or os.path.join(model_dir, f'recommend_{args.load_ckpt_name}.tsv')
     out = write_recommendations(model, users_test, hist_test, emb, args.topk, 256, args, user_names, item_names, out,
-                                candidates=read_candidates(args.candidate_items, item_names) if args.candidate_items else None)
+                                candidates=read_candidates(args.candidate_items, item_names) if args.candidate_items else None,
+                                candidate_lists=read_candidate_lists(args.candidate_lists, user_names, item_names) if args.candidate_lists else None)
     if out:
         Log_file.info(f'recommend: top-{args.topk} lists of {len(users_test)} users -> {out}')
 

@@ -13,6 +13,7 @@ import torch
 import torch.distributed as dist
 
 from .. import _lib as L
+from .._lib_user_lists import LIST_MAX
 from .dataset import SequentialDistributedSampler
 
 
@@ -168,11 +169,15 @@ def read_candidates(path, item_names):
 
 
 def check_candidate_flag(args):
-    """--candidate_items restricts --mode test and --mode recommend; training and its per-epoch evaluation are not restricted by it, so any
-    other mode refuses the flag instead of ignoring it."""
-    if getattr(args, 'candidate_items', None) and not ('test' in args.mode or args.mode == 'recommend'):
-        raise ValueError(f'--candidate_items is honoured by --mode test and --mode recommend only, not by --mode {args.mode} '
-                         '(training and its per-epoch evaluation range over the whole catalogue)')
+    """--candidate_items and --candidate_lists restrict --mode test and --mode recommend; training and its per-epoch evaluation are not
+    restricted by them, so any other mode refuses either flag instead of ignoring it.  The two together are refused as well: a user's own list
+    is the restriction, not one more beside a shared set."""
+    for flag in ('candidate_items', 'candidate_lists'):
+        if getattr(args, flag, None) and not ('test' in args.mode or args.mode == 'recommend'):
+            raise ValueError(f'--{flag} is honoured by --mode test and --mode recommend only, not by --mode {args.mode} '
+                             '(training and its per-epoch evaluation range over the whole catalogue)')
+    if getattr(args, 'candidate_items', None) and getattr(args, 'candidate_lists', None):
+        raise ValueError('--candidate_lists (a list per user) and --candidate_items (one set for all users) cannot be combined: give one of them')
 
 
 def candidates_from_args(args, behaviors_path, name2id, Log_file):
@@ -187,9 +192,93 @@ def candidates_from_args(args, behaviors_path, name2id, Log_file):
     return mask
 
 
-def eval_ranks(model, user_history, eval_seq, item_embeddings, test_batch_size, args, user_ids, candidates=None):
+def _user_list(candidate_lists, u):
+    """user u's entry of ``candidate_lists`` (a mapping, or a sequence indexed by user id), None where there is none"""
+    if hasattr(candidate_lists, 'get'):
+        return candidate_lists.get(u)
+    return candidate_lists[u] if 0 <= u < len(candidate_lists) else None
+
+
+def has_candidate_list(candidate_lists, uids):
+    """bool [n]: whether each listed user has an entry in ``candidate_lists`` (an empty list is one)"""
+    return np.fromiter((_user_list(candidate_lists, int(u)) is not None for u in uids), dtype=bool, count=len(uids))
+
+
+def candidate_lists_csr(candidate_lists, uids):
+    """The listed users' own candidate lists as a4r_topk_lists / a4r_eval_rank_lists read them: (ptr int64 [n + 1], flat int32 ids + one spare 0,
+    lens int64 [n]), built on the host.  A user without an entry gets an empty list.  Ids outside int32 are clamped to -1 (ignored like any id
+    outside 1 .. N).  A list longer than LIST_MAX raises ValueError naming the user: it is never truncated."""
+    ls = []
+    for u in uids:
+        e = _user_list(candidate_lists, int(u))
+        x = np.zeros(0, np.int64) if e is None else np.asarray(e if isinstance(e, (np.ndarray, torch.Tensor)) else list(e), dtype=np.int64).reshape(-1)
+        if x.size > LIST_MAX:
+            raise ValueError(f'user {int(u)}: candidate list of {x.size} items exceeds A4R_LIST_MAX = {LIST_MAX} (never truncated); '
+                             'a catalogue-scale set belongs in a shared candidate set (--candidate_items)')
+        ls.append(x)
+    lens = np.fromiter((x.size for x in ls), dtype=np.int64, count=len(ls))
+    ptr = np.zeros(len(ls) + 1, dtype=np.int64)
+    np.cumsum(lens, out=ptr[1:])
+    flat = np.concatenate(ls + [np.zeros(1, np.int64)])
+    flat = np.where((flat < 0) | (flat > np.iinfo(np.int32).max), -1, flat).astype(np.int32)
+    return ptr, flat, lens
+
+
+def _both_refused(candidates, candidate_lists):
+    if candidates is not None and candidate_lists is not None:
+        raise ValueError('candidates (one set for all users) and candidate_lists (a list per user) cannot be combined: give one of them')
+
+
+def read_candidate_lists(path, user_names, item_names):
+    """A candidate-list file -> {uid: [item ids]}: one line per user, ``user_name \\t item_name item_name ...`` with the names --mode recommend
+    writes (``user_names[uid]``, ``item_names[i]`` with [0] = the pad item: preprocess.read_behavior_names).  Blank lines are ignored; a user
+    named twice has the second line appended; a user named without items has an empty list.  Names that are no user or no item raise ValueError
+    listing the first few."""
+    users = {name: u for u, name in enumerate(user_names)}
+    items = {name: i for i, name in enumerate(item_names) if i > 0 and name is not None}
+    out, bad_users, bad_items = {}, [], []
+    with open(path) as f:
+        for line in f:
+            if not line.strip():
+                continue
+            head, _, rest = line.rstrip('\n').partition('\t')
+            u = users.get(head.strip())
+            if u is None:
+                if head.strip() not in bad_users:
+                    bad_users.append(head.strip())
+                continue
+            ids = out.setdefault(u, [])
+            for name in rest.split():
+                i = items.get(name)
+                if i is None:
+                    if name not in bad_items:
+                        bad_items.append(name)
+                else:
+                    ids.append(i)
+    for bad, what in ((bad_users, 'user'), (bad_items, 'item')):
+        if bad:
+            raise ValueError(f'{path}: {len(bad)} name(s) that are no {what} of this dataset: ' + ', '.join(bad[:5]) + (' ...' if len(bad) > 5 else ''))
+    return out
+
+
+def candidate_lists_from_args(args, behaviors_path, name2id, Log_file):
+    """The runners' --candidate_lists FILE -> {uid: [item ids]} in the numbering read_behaviors gives users and items, or None without the flag."""
+    if not getattr(args, 'candidate_lists', None):
+        return None
+    from .preprocess import read_behavior_names
+    user_names, item_names = read_behavior_names(behaviors_path, name2id, args.max_seq_len, args.min_seq_len)
+    lists = read_candidate_lists(args.candidate_lists, user_names, item_names)
+    Log_file.info(f'candidate lists: {len(lists)} of {len(user_names)} users, {sum(len(v) for v in lists.values())} items in all, from {args.candidate_lists}')
+    return lists
+
+
+def eval_ranks(model, user_history, eval_seq, item_embeddings, test_batch_size, args, user_ids, candidates=None, candidate_lists=None):
     """Rank (1 = best) of each listed user's held-out target among all items not in the user's history.  ``candidates`` (candidate_mask's
-    input): among the candidate items only -- for every listed user; a target that is no candidate gets the rank it would have if it were."""
+    input): among the candidate items only -- for every listed user; a target that is no candidate gets the rank it would have if it were.
+    ``candidate_lists`` (a mapping, or a sequence indexed by user id, from user to an iterable of item ids, at most LIST_MAX each): among the
+    user's own listed items only (a4r_eval_rank_lists: a sampled evaluation's negatives); a user without a list gets rank 1, the target need
+    not be listed."""
+    _both_refused(candidates, candidate_lists)
     inner = _inner(model, args)
     dev = next(model.parameters()).device
     emb = item_embeddings.to(dev).float().contiguous()
@@ -203,6 +292,9 @@ def eval_ranks(model, user_history, eval_seq, item_embeddings, test_batch_size, 
     # (the sampler pads its tail by REPEATING the last user: a repeated id takes the rank of the entry before it)
     first = np.concatenate([[True], np.diff(uid_all) != 0])
     uid_np = uid_all[first]
+    if candidate_lists is not None:                               # the CSR of the users' own lists, uploaded once, sliced per batch
+        lptr, lflat_np, llens = candidate_lists_csr(candidate_lists, uid_np)
+        lflat = torch.from_numpy(lflat_np).to(dev)
     # SequentialDistributedSampler hands every rank a run of consecutive users (its tail repeats the last ones): a batch of CONSECUTIVE users is a
     # slice of every prepared tensor -- no gather, no host-device round trip for the history count
     runs = np.flatnonzero(np.diff(uid_np) != 1) + 1
@@ -224,7 +316,11 @@ def eval_ranks(model, user_history, eval_seq, item_embeddings, test_batch_size, 
                 ptr = (P['hptr'][a:b + 1] - h0).to(torch.int32)
                 hist = P['hflat32'][h0:h1 + 1]                 # (+ 1: the kernel's table is never empty; the store ends in one spare 0)
                 rank = torch.zeros(nb, dtype=torch.int32, device=dev)
-                if cand is None:
+                if candidate_lists is not None:
+                    l0, l1 = int(lptr[s0]), int(lptr[s0 + nb])
+                    L.eval_rank_lists(prec, emb, P['target32'][a:b], torch.from_numpy((lptr[s0:s0 + nb + 1] - l0).astype(np.int32)).to(dev),
+                                      lflat[l0:l1 + 1], int(llens[s0:s0 + nb].max()), ptr, hist, rank)
+                elif cand is None:
                     L.eval_rank(prec, emb, P['target32'][a:b], ptr, hist, rank)
                 else:
                     L.eval_rank_cand(prec, emb, P['target32'][a:b], ptr, hist, cand, rank)
@@ -235,10 +331,15 @@ def eval_ranks(model, user_history, eval_seq, item_embeddings, test_batch_size, 
     return out
 
 
-def eval_model(model, user_history, eval_seq, item_embeddings, test_batch_size, args, item_num, Log_file, v_or_t, local_rank, candidates=None):
+def eval_model(model, user_history, eval_seq, item_embeddings, test_batch_size, args, item_num, Log_file, v_or_t, local_rank, candidates=None,
+               candidate_lists=None):
     """metrics.py:82-116.  Returns mean Hit@10 over all users (ranks are gathered over the data-parallel group).  ``candidates``
     (candidate_mask's input): every target is ranked among the candidate items only, and the means run over the users whose target is a
-    candidate (cold-start and split evaluation); ValueError when there is no such user."""
+    candidate (cold-start and split evaluation); ValueError when there is no such user.  ``candidate_lists`` (eval_ranks'): every target is
+    ranked among the user's own listed items, and the means run over the users who have a list; ValueError when no user has one."""
+    _both_refused(candidates, candidate_lists)
+    if candidate_lists is not None:
+        return _eval_model_lists(model, user_history, eval_seq, item_embeddings, test_batch_size, args, Log_file, v_or_t, candidate_lists)
     if candidates is not None:
         return _eval_model_candidates(model, user_history, eval_seq, item_embeddings, test_batch_size, args, Log_file, v_or_t, candidates)
     world = dist.get_world_size() if dist.is_initialized() else 1
@@ -280,6 +381,28 @@ def _eval_model_candidates(model, user_history, eval_seq, item_embeddings, test_
     P = _prepare_eval_set(eval_seq, user_history, args.max_seq_len + 1, dev)
     uid = torch.from_numpy(np.asarray(user_ids, dtype=np.int64)).to(dev)
     valid = (cand[P['target'][uid]] != 0).float() if uid.numel() else torch.zeros(0, device=dev)
+    return _means_over_valid(ranks, valid, n_users, topK, world, Log_file, v_or_t, 'candidates', 'has a target among the candidate items')
+
+
+def _eval_model_lists(model, user_history, eval_seq, item_embeddings, test_batch_size, args, Log_file, v_or_t, candidate_lists):
+    """eval_model within each user's own candidate list: as _eval_model_candidates, the validity flag being "the user has a list"."""
+    world = dist.get_world_size() if dist.is_initialized() else 1
+    rank_id = dist.get_rank() if dist.is_initialized() else 0
+    n_users = len(eval_seq)
+    sampler = SequentialDistributedSampler(range(n_users), test_batch_size, rank=rank_id, num_replicas=world)
+    user_ids = sampler.indices()
+    model.eval()
+    topK = 10
+    dev = next(model.parameters()).device
+    Log_file.info(v_or_t + '_methods   {}'.format('\t'.join(['Hit{}'.format(topK), 'nDCG{}'.format(topK)])))
+    ranks = eval_ranks(model, user_history, eval_seq, item_embeddings, test_batch_size, args, user_ids, candidate_lists=candidate_lists).float()
+    valid = torch.from_numpy(has_candidate_list(candidate_lists, user_ids).astype(np.float32)).to(dev)
+    return _means_over_valid(ranks, valid, n_users, topK, world, Log_file, v_or_t, 'candidate_lists', 'has a candidate list')
+
+
+def _means_over_valid(ranks, valid, n_users, topK, world, Log_file, v_or_t, label, what):
+    """Hit@topK / nDCG@topK as means over the users whose validity flag is set (gathered over the data-parallel group beside hit and ndcg), the
+    metrics line and ``<v_or_t>_<label>   k of n users``; ValueError when no user qualifies."""
     hit = (ranks <= topK).float() * valid
     ndcg = torch.where(ranks <= topK, 1.0 / torch.log2(ranks + 1.0), torch.zeros_like(ranks)) * valid
     if world > 1:
@@ -289,10 +412,10 @@ def _eval_model_candidates(model, user_history, eval_seq, item_embeddings, test_
         hit, ndcg, valid = (torch.cat(p) for p in parts)
     k = int(valid[:n_users].sum().item())
     if k == 0:
-        raise ValueError(f'{v_or_t}: no user of {n_users} has a target among the candidate items')
+        raise ValueError(f'{v_or_t}: no user of {n_users} {what}')
     mean_eval = [float(hit[:n_users].sum().item()) / k, float(ndcg[:n_users].sum().item()) / k]
     print_metrics(mean_eval, Log_file, v_or_t)
-    Log_file.info(v_or_t + '_candidates   {} of {} users'.format(k, n_users))
+    Log_file.info(v_or_t + '_{}   {} of {} users'.format(label, k, n_users))
     return mean_eval[0]
 
 
@@ -324,7 +447,7 @@ def _recommend_inputs(user_seqs, exclude, uids, T):
     return ids, mask, ptr, flat
 
 
-def recommend(model, user_seqs, item_embeddings, k, args, exclude=None, user_ids=None, candidates=None):
+def recommend(model, user_seqs, item_embeddings, k, args, exclude=None, user_ids=None, candidates=None, candidate_lists=None):
     """The k best items for each listed user (default: every user of ``user_seqs``), after the user's sequence.
 
     ``user_seqs[u]``: the user's item ids (1 .. N); its last ``max_seq_len`` items go through ``user_encoder``, left-padded as an evaluation
@@ -334,7 +457,10 @@ def recommend(model, user_seqs, item_embeddings, k, args, exclude=None, user_ids
     Returns (ids LongTensor [U, k], scores fp32 [U, k]) on the model's device: score descending, ties by smaller id; a user with fewer than k
     candidates gets id 0 / score -inf in the remaining slots.  One a4r_topk_items launch pair per batch of users (the [users, items] score matrix
     is never formed).  ``candidates`` (candidate_mask's input: bool / uint8 [N + 1], one set for all users): the lists are drawn from the
-    candidate items only (a4r_topk_items_cand) -- the catalogue in stock, say, which no 264-id exclusion list could express."""
+    candidate items only (a4r_topk_items_cand) -- the catalogue in stock, say, which no 264-id exclusion list could express.
+    ``candidate_lists`` (eval_ranks': user -> an iterable of item ids, at most LIST_MAX each, longer lists raise ``ValueError``): the k best of
+    the user's own listed items (a4r_topk_lists) -- a retrieval stage's shortlist, re-ranked; a user without a list gets pad slots only."""
+    _both_refused(candidates, candidate_lists)
     inner = _inner(model, args)
     dev = next(model.parameters()).device
     emb = item_embeddings.to(dev).float().contiguous()
@@ -348,6 +474,9 @@ def recommend(model, user_seqs, item_embeddings, k, args, exclude=None, user_ids
     ids_np, mask_np, ptr_np, flat_np = _recommend_inputs(user_seqs, exclude, uids, T)
     step = int(os.environ.get('A4R_EVAL_USER_BATCH', 0)) or 8192          # (eval_ranks' user batch)
     flat = torch.from_numpy(flat_np).to(dev)
+    if candidate_lists is not None:                               # the CSR of the users' own lists, uploaded once, sliced per batch
+        lptr, lflat_np, llens = candidate_lists_csr(candidate_lists, uids)
+        lflat = torch.from_numpy(lflat_np).to(dev)
     out_ids, out_scores = [], []
     model.eval()
     with torch.no_grad():
@@ -361,7 +490,11 @@ def recommend(model, user_seqs, item_embeddings, k, args, exclude=None, user_ids
             ptr = torch.from_numpy((ptr_np[a:b + 1] - h0).astype(np.int32)).to(dev)
             ids = torch.empty(nb, k, dtype=torch.int32, device=dev)
             scores = torch.empty(nb, k, dtype=torch.float32, device=dev)
-            if cand is None:
+            if candidate_lists is not None:
+                l0, l1 = int(lptr[a]), int(lptr[b])
+                L.topk_lists(prec, emb, torch.from_numpy((lptr[a:b + 1] - l0).astype(np.int32)).to(dev), lflat[l0:l1 + 1], int(llens[a:b].max()),
+                             ptr, flat[h0:h1 + 1], k, ids, scores)
+            elif cand is None:
                 L.topk_items(prec, emb, ptr, flat[h0:h1 + 1], k, ids, scores)
             else:
                 L.topk_items_cand(prec, emb, ptr, flat[h0:h1 + 1], cand, k, ids, scores)
@@ -370,12 +503,13 @@ def recommend(model, user_seqs, item_embeddings, k, args, exclude=None, user_ids
     return torch.cat(out_ids), torch.cat(out_scores)
 
 
-def write_recommendations(model, user_seqs, user_history, item_embeddings, k, batch_size, args, user_names, item_names, path, candidates=None):
+def write_recommendations(model, user_seqs, user_history, item_embeddings, k, batch_size, args, user_names, item_names, path, candidates=None,
+                          candidate_lists=None):
     """The runners' --mode recommend: the k next items after every user's whole known sequence (``user_seqs[u]``, the evaluation input of the
     test split, whose last item is the held-out one), excluding ``user_history[u]`` plus that last item -- everything the user is known to have
     seen.  Users are sharded over the data-parallel ranks as eval_model shards them; rank 0 writes ``path``: one line per user, in uid order,
     ``user_name \\t item_1 ... item_k \\t score_1 ... score_k`` with the item file's names (pad slots of a short list omitted).
-    ``candidates``: as recommend's."""
+    ``candidates``, ``candidate_lists``: as recommend's; under ``candidate_lists`` a user without a list gets no line."""
     world = dist.get_world_size() if dist.is_initialized() else 1
     rank_id = dist.get_rank() if dist.is_initialized() else 0
     n_users = len(user_seqs)
@@ -385,7 +519,8 @@ def write_recommendations(model, user_seqs, user_history, item_embeddings, k, ba
         u = int(u)
         if u not in exclude:
             exclude[u] = np.concatenate([np.asarray(user_history[u], dtype=np.int64).reshape(-1), np.asarray(user_seqs[u][-1:], dtype=np.int64)])
-    ids, scores = recommend(model, user_seqs, item_embeddings, k, args, exclude=exclude, user_ids=uids, candidates=candidates)
+    ids, scores = recommend(model, user_seqs, item_embeddings, k, args, exclude=exclude, user_ids=uids, candidates=candidates,
+                            candidate_lists=candidate_lists)
     if world > 1:
         parts_i = [torch.zeros_like(ids) for _ in range(world)]
         parts_s = [torch.zeros_like(scores) for _ in range(world)]
@@ -395,8 +530,11 @@ def write_recommendations(model, user_seqs, user_history, item_embeddings, k, ba
     if rank_id != 0:
         return None
     ids, scores = ids[:n_users].cpu().numpy(), scores[:n_users].cpu().numpy()
+    listed = np.ones(n_users, bool) if candidate_lists is None else has_candidate_list(candidate_lists, range(n_users))
     with open(path, 'w') as f:
         for u in range(n_users):
+            if not listed[u]:
+                continue
             keep = ids[u] != 0
             f.write(user_names[u] + '\t' + ' '.join(item_names[int(i)] for i in ids[u][keep]) + '\t'
                     + ' '.join('%.9g' % float(s) for s in scores[u][keep]) + '\n')

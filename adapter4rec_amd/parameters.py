@@ -40,6 +40,7 @@ def build_parser():
     p.add_argument('--topk', type=int, default=10)                     # --mode recommend: items per user
     p.add_argument('--recommend_out', type=str, default=None)          # --mode recommend: output file (default <model_dir>/recommend_<load_ckpt_name>.tsv)
     p.add_argument('--candidate_items', type=str, default=None)        # --mode test / recommend: a file of item names, one per line -- rank and recommend among these items only
+    p.add_argument('--candidate_lists', type=str, default=None)        # --mode test / recommend: a file of `user_name \t item_name item_name ...` lines -- rank and recommend within each user's own list
     p.add_argument('--label_screen', type=str, default='None')
     p.add_argument('--logging_num', type=int, default=8)
     p.add_argument('--testing_num', type=int, default=1)

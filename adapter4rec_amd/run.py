@@ -18,7 +18,8 @@ from torch.utils.data import DataLoader
 
 from .data_utils import (BuildTrainDataset, eval_model, get_doc_input_bert, get_item_embeddings, read_behaviors,
                          read_news_bert)
-from .data_utils.metrics import candidate_mask, candidates_from_args, check_candidate_flag, read_candidates, write_recommendations
+from .data_utils.metrics import (candidate_lists_from_args, candidate_mask, candidates_from_args, check_candidate_flag, read_candidate_lists, read_candidates,
+                                 write_recommendations)
 from .data_utils.preprocess import read_behavior_names
 from .data_utils.dataset import DeviceTrainSampler
 from .data_utils.utils import (get_checkpoint, para_and_log, report_time_eval, report_time_train, save_model, setuplogger)
@@ -90,11 +91,13 @@ def build_model(args, item_num, use_modal, bert_model, local_rank, Log_file, mod
     return model.to(local_rank), start_epoch, ckpt2
 
 
-def run_eval_once(model, item_content, user_history, users_eval, batch_size, item_num, use_modal, mode, local_rank, args, Log_file, candidates=None):
+def run_eval_once(model, item_content, user_history, users_eval, batch_size, item_num, use_modal, mode, local_rank, args, Log_file, candidates=None, candidate_lists=None):
     t0 = time.time()
     Log_file.info('Validating...')
     emb = get_item_embeddings(model, item_content, batch_size, args, use_modal, local_rank)
     kw = {} if candidates is None else dict(candidates=candidates)      # --candidate_items: ranked among, and averaged over targets within, the candidate set
+    if candidate_lists is not None:                                     # --candidate_lists: ranked within the user's own list, averaged over the users who have one
+        kw = dict(candidate_lists=candidate_lists)
     hit10 = eval_model(model, user_history, users_eval, emb, batch_size, args, item_num, Log_file, mode, local_rank, **kw)
     report_time_eval(t0, Log_file)
     return hit10
@@ -199,6 +202,9 @@ def test(args, use_modal, local_rank, Log_file, Log_screen, model_dir, start_tim
     cand = candidates_from_args(args, os.path.join(args.root_data_dir, args.dataset, args.behaviors), before_name2id, Log_file)
     # --candidate_items: the mask is uploaded once, for both splits; without the flag the calls are the ones made before
     kw = {} if cand is None else dict(candidates=candidate_mask(cand, item_num + 1, next(model.parameters()).device))
+    lists = candidate_lists_from_args(args, os.path.join(args.root_data_dir, args.dataset, args.behaviors), before_name2id, Log_file)
+    if lists is not None:                                              # --candidate_lists (never beside --candidate_items: main refuses the pair)
+        kw = dict(candidate_lists=lists)
     run_eval_once(model, item_content, hist_valid, users_valid, 512, item_num, use_modal, 'valid', local_rank, args, Log_file, **kw)
     run_eval_once(model, item_content, hist_test, users_test, 512, item_num, use_modal, 'test', local_rank, args, Log_file, **kw)
 
@@ -220,7 +226,8 @@ def recommend(args, use_modal, local_rank, Log_file, Log_screen, model_dir, star
     model = FlatDDP(model, device_ids=[local_rank], output_device=local_rank)
     emb = get_item_embeddings(model, item_content, 512, args, use_modal, local_rank)
     out = write_recommendations(model, users_test, hist_test, emb, args.topk, 512, args, user_names, item_names, recommend_out_path(args, model_dir),
-                                candidates=read_candidates(args.candidate_items, item_names) if args.candidate_items else None)
+                                candidates=read_candidates(args.candidate_items, item_names) if args.candidate_items else None,
+                                candidate_lists=read_candidate_lists(args.candidate_lists, user_names, item_names) if args.candidate_lists else None)
     if out:
         Log_file.info(f'recommend: top-{args.topk} lists of {len(users_test)} users -> {out}')
 

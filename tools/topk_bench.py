@@ -2,9 +2,12 @@
 """Top-K recommendation on one MI355X: a4r_topk_items beside a4r_eval_rank (the same scoring sweep, one rank per user) and beside the torch path a
 user would otherwise write (chunked fp32 matmul, history masked, torch.topk), and recommend() end to end -- one JSON line per configuration.
 
-    python tools/topk_bench.py [--iters N] [--only NAME] [--candidates FRACTION]
+    python tools/topk_bench.py [--iters N] [--only NAME] [--candidates FRACTION] [--lists C]
 
 --candidates FRACTION runs the candidate-set leg instead (cand_cfg): a4r_topk_items_cand / a4r_eval_rank_cand beside the unmasked entries, interleaved.
+--lists C runs the per-user-list leg instead (lists_cfg): a4r_topk_lists over C listed items per user (C = 0: 100, 1000 and 4096 in turn), E = 64 and
+128, beside the eager path a caller without the kernel writes (chunked emb[idx] gather, einsum, exclusion mask, torch.topk), interleaved, and beside
+a4r_topk_items over the whole table for scale.
 
 Shapes: 32 768 users x 65 537 items (the evaluation benchmark's shape) and x 500 001 items (the ID tower's 500 000-item table), E = 64, K 10 / 100,
 histories of 20 uniform ids.  Kernel times are HIP-event means over N launches after a warm-up; per-kernel times: run this under
@@ -97,6 +100,53 @@ def cand_cfg(name, U, N1, E, k, fraction, iters, rounds=2, H=20):
                 eval_rank_cand_over_eval_rank=round(min(ms['eval_rank_cand']) / min(ms['eval_rank']), 3))
 
 
+def eager_lists(prec, emb, idx, hist, k, chunk):
+    """what a caller without the kernel writes: gather the listed rows of a chunk of users, one dot product per row, the user's history masked,
+    torch.topk, the ids looked up (the lists here hold distinct items, so nothing has to be deduplicated)"""
+    ids, scores = [], []
+    for a in range(0, prec.shape[0], chunk):
+        ix = idx[a:a + chunk].long()
+        s = torch.einsum('uce,ue->uc', emb[ix], prec[a:a + chunk])
+        s.masked_fill_((ix[:, :, None] == hist[a:a + chunk].long()[:, None, :]).any(-1), -float('inf'))
+        v, i = torch.topk(s, k, dim=1)
+        ids.append(torch.gather(ix, 1, i))
+        scores.append(v)
+    return torch.cat(ids), torch.cat(scores)
+
+
+def lists_cfg(name, U, N1, E, k, C, iters, rounds=2, H=20):
+    """--lists C: every user lists C distinct items (a random start and an odd stride through the N1 - 1 = 2^16 items); a4r_topk_lists and the
+    eager path interleaved `rounds` times, every round's mean reported; a4r_topk_items over the whole table once, for scale.  gather_GBps: the
+    listed rows' bytes, U * C * E * 4, over the kernel's best time."""
+    from adapter4rec_amd import _lib as L
+    assert (N1 - 1) & (N1 - 2) == 0 and C <= N1 - 1
+    emb, prec, hist, ptr, tgt = data(U, N1, E, H)
+    flat = hist.reshape(-1).contiguous()
+    g = torch.Generator(device=DEV).manual_seed(2)
+    start = torch.randint(0, N1 - 1, (U, 1), device=DEV, generator=g)
+    stride = torch.randint(0, (N1 - 1) // 2, (U, 1), device=DEV, generator=g) * 2 + 1
+    idx = ((start + stride * torch.arange(C, device=DEV)[None]) % (N1 - 1) + 1).to(torch.int32).contiguous()
+    lptr = (torch.arange(U + 1, device=DEV, dtype=torch.int32) * C).contiguous()
+    lflat = idx.reshape(-1)
+    ids = torch.empty(U, k, dtype=torch.int32, device=DEV)
+    sc = torch.empty(U, k, dtype=torch.float32, device=DEV)
+    chunk = max(1, (1 << 28) // (C * E))                            # 1 GiB of gathered rows per chunk
+    legs = dict(topk_lists=lambda: L.topk_lists(prec, emb, lptr, lflat, C, ptr, flat, k, ids, sc), eager=lambda: eager_lists(prec, emb, idx, hist, k, chunk))
+    ms = {n: [] for n in legs}
+    for _ in range(rounds):
+        for n, fn in legs.items():
+            ms[n].append(round(timed(fn, iters if n == 'topk_lists' else max(1, iters // 4)), 4))
+    ei, _ = eager_lists(prec, emb, idx, hist, k, chunk)
+    legs['topk_lists']()
+    agree = float((ei.int() == ids).float().mean())                 # random fp32 data: the lists agree up to near-ties
+    ids_t = torch.empty(U, k, dtype=torch.int32, device=DEV)
+    t_table = timed(lambda: L.topk_items(prec, emb, ptr, flat, k, ids_t, sc), max(1, iters // 4))
+    best = min(ms['topk_lists'])
+    return dict(name=name, users=U, items=N1, E=E, k=k, listed=C, rounds=rounds, iters=iters, **{n + '_ms': v for n, v in ms.items()},
+                eager_over_topk_lists=round(min(ms['eager']) / best, 2), users_per_s=round(U / best * 1e3),
+                gather_GBps=round(U * C * E * 4 / best / 1e6, 1), topk_items_whole_table_ms=round(t_table, 4), id_agreement_with_eager=round(agree, 6))
+
+
 def recommend_cfg(name, U, item_num, k, iters, T=20):
     from adapter4rec_amd.cv import Model
     from adapter4rec_amd.cv.data_utils import get_itemId_embeddings
@@ -123,7 +173,16 @@ def main():
     ap.add_argument('--only', default=None)
     ap.add_argument('--candidates', type=float, default=None, metavar='FRACTION',
                     help='run the candidate-set leg instead: the masked entries beside the unmasked ones under a random mask of this fraction')
+    ap.add_argument('--lists', type=int, default=None, metavar='C', choices=(0, 100, 1000, 4096),
+                    help="run the per-user-list leg instead: a4r_topk_lists over C listed items per user beside the eager gather path (0: every C)")
     a = ap.parse_args()
+    if a.lists is not None:
+        for C in ((100, 1000, 4096) if a.lists == 0 else (a.lists,)):
+            for E in (64, 128):
+                name = f'lists_c{C}_e{E}'
+                if not a.only or a.only == name:
+                    print(json.dumps(lists_cfg(name, 32768, 65537, E, 10, C, a.iters if C < 4096 else max(2, a.iters // 4))), flush=True)
+        return
     if a.candidates is not None:
         for name, N1, it in (('cand_k10_65537', 65537, a.iters), ('cand_k10_500000', 500000, max(1, a.iters // 4))):
             if not a.only or a.only == name:
