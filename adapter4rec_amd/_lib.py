@@ -544,12 +544,25 @@ def quant_rows_fp8(x, q, scale, M=None):
     _check(lib().a4r_quant_rows_fp8(_stream(), _p(x), _ld(x), _p(q), _ld(q), _p(scale), M, x.shape[1], _dt(x)), 'a4r_quant_rows_fp8')
 
 
+def _ln_operands(M, H, gamma, beta=None, stats=None, add=None):
+    """What the LayerNorm kernels read through a bare pointer: gamma / beta as H contiguous fp32, add as contiguous [add_rows, H] fp32 (its leading
+    dimension IS H), stats as contiguous [>= M, 2] fp32.  A strided view would be misread silently."""
+    f32 = torch.float32
+    assert gamma.dtype is f32 and gamma.is_contiguous() and gamma.numel() >= H, f'gamma: {H} contiguous fp32 values expected'
+    assert beta is None or (beta.dtype is f32 and beta.is_contiguous() and beta.numel() >= H), f'beta: {H} contiguous fp32 values expected'
+    assert add is None or (add.dtype is f32 and add.dim() == 2 and add.shape[1] == H and add.shape[0] > 0 and add.is_contiguous()), \
+        'add: a contiguous fp32 [add_rows, H] table expected'
+    assert stats is None or (stats.dtype is f32 and stats.dim() == 2 and stats.shape[1] == 2 and stats.shape[0] >= M and stats.is_contiguous()), \
+        'stats: contiguous fp32 [>= M, 2] expected'
+
+
 def ln_fwd_sum(h, res, gamma, beta, eps, y, stats, M=None, res32=None, sum_out=None, sum32=None, y32=None):
     """y = LN(h + residual), sum in fp32, normalised unrounded; residual = res32 (fp32) when given, else res (h's dtype).  Optional outputs:
     sum_out (h's dtype), sum32, y32 (fp32)."""
     require_gpu(h, res, res32, y, sum_out, sum32, y32)
     M = h.shape[0] if M is None else M
     assert res32 is not None or res is not None
+    _ln_operands(M, h.shape[1], gamma, beta, stats)
     _check(lib().a4r_ln_fwd_sum(_stream(), _p(h), _ld(h), _p(res32), _ld0(res32), _p(res), _ld0(res), _p(gamma), _p(beta), eps, _p(y), _ld(y), _p(sum_out), _ld0(sum_out),
                                 _p(sum32), _ld0(sum32), _p(y32), _ld0(y32), _p(stats), M, h.shape[1], _dt(h)), 'a4r_ln_fwd_sum')
 
@@ -557,6 +570,7 @@ def ln_fwd_sum(h, res, gamma, beta, eps, y, stats, M=None, res32=None, sum_out=N
 def ln_fwd(v, gamma, beta, eps, y, stats, M=None, add=None, drop_p=0.0, drop_site=0, drop_seed=0, y8=None, ys=None):
     require_gpu(v, y, y8)
     M = v.shape[0] if M is None else M
+    _ln_operands(M, v.shape[1], gamma, beta, stats, add)
     if y8 is not None:                    # also emit the row as e4m3 + per-row scale (y may be None)
         assert drop_p == 0.0 and y8.dtype == torch.uint8 and ys.dtype == torch.float32
         _check(lib().a4r_ln_fwd_fp8(_stream(), _p(v), _ld(v), _p(add), add.shape[0] if add is not None else 0, _p(gamma), _p(beta), eps, _p(y), _ld0(y), _p(y8), _ld(y8), _p(ys),
@@ -570,6 +584,7 @@ def ln_bwd(dy, v, stats, gamma, dv, M=None, add=None, dgamma=None, dbeta=None, d
            drop_p=0.0, drop_site=0, drop_seed=0, dv2=None, drop2_p=0.0, drop2_site=0, drop2_seed=0):
     require_gpu(dy, v, dv)
     M = v.shape[0] if M is None else M
+    _ln_operands(M, v.shape[1], gamma, None, stats, add)
     _check(lib().a4r_ln_bwd(_stream(), _p(dy), _ld(dy), _p(v), _ld(v), _p(add), add.shape[0] if add is not None else 0, _p(stats), _p(gamma), _p(dres), _ld0(dres), _p(dv), _ld(dv),
                             _p(dgamma), _p(dbeta), _p(dbias), M, v.shape[1], _dt(v), drop_p, drop_site, drop_seed, _p(dv2), _ld0(dv2), drop2_p, drop2_site, drop2_seed),
            'a4r_ln_bwd')

@@ -883,7 +883,7 @@ extern "C" int a4r_ln_bwd(void* stream, const void* dy, int lddy, const void* v,
 static int rows_copy(void* stream, const void* in, int ldi, void* out, int ldo, int n, int row_step, int H, int dtype, bool scatter) {
     if (!in || !out || bad_dtype(dtype) || n <= 0 || row_step <= 0 || H <= 0) return A4R_EINVAL;
     const int esz = dtype == A4R_F32 ? 4 : 2;
-    if ((H * esz) % 16 || (ldi * esz) % 16 || (ldo * esz) % 16 || misaligned(in) || misaligned(out)) return A4R_EINVAL;
+    if ((H * esz) % 16 || (ldi * esz) % 16 || (ldo * esz) % 16 || ldi < H || ldo < H || misaligned(in) || misaligned(out)) return A4R_EINVAL;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const size_t total = (size_t)n * (H * esz / 16);
     int grid = (int)((total + 255) / 256); if (grid > 2048) grid = 2048;

@@ -450,8 +450,13 @@ def ln_fwd_sum(h, res, gamma, beta, eps, y, stats, M=None, res32=None, sum_out=N
         y32[:M] = out
 
 
+def _row_keep(M, H, p, site, seed):
+    """keep * keep_scale of the [M, H] rows from the host restatement of the kernels' hash (oracle/dropout_masks.py, element row * H + col)"""
+    from oracle.dropout_masks import DropoutStream
+    return DropoutStream(seed).mask('rows', site, torch.empty(M, H), p)
+
+
 def ln_fwd(v, gamma, beta, eps, y, stats, M=None, add=None, drop_p=0.0, drop_site=0, drop_seed=0, y8=None, ys=None):
-    assert drop_p == 0.0
     M = v.shape[0] if M is None else M
     x = v[:M].float()
     if add is not None:
@@ -463,6 +468,8 @@ def ln_fwd(v, gamma, beta, eps, y, stats, M=None, add=None, drop_p=0.0, drop_sit
         stats[:M, 0] = mu[:, 0]
         stats[:M, 1] = rstd[:, 0]
     out = (x - mu) * rstd * gamma + beta
+    if drop_p > 0:
+        out = out * _row_keep(M, v.shape[1], drop_p, drop_site, drop_seed)
     if y is not None:
         y[:M] = out.to(y.dtype)
     if y8 is not None:
@@ -471,7 +478,6 @@ def ln_fwd(v, gamma, beta, eps, y, stats, M=None, add=None, drop_p=0.0, drop_sit
 
 def ln_bwd(dy, v, stats, gamma, dv, M=None, add=None, dgamma=None, dbeta=None, dbias=None, dres=None,
            drop_p=0.0, drop_site=0, drop_seed=0, dv2=None, drop2_p=0.0, drop2_site=0, drop2_seed=0):
-    assert drop_p == 0.0 and drop2_p == 0.0
     M = v.shape[0] if M is None else M
     x = v[:M].float()
     if add is not None:
@@ -479,6 +485,8 @@ def ln_bwd(dy, v, stats, gamma, dv, M=None, add=None, dgamma=None, dbeta=None, d
     mu, rstd = stats[:M, 0:1], stats[:M, 1:2]
     xh = (x - mu) * rstd
     d = dy[:M].float()
+    if drop_p > 0:
+        d = d * _row_keep(M, v.shape[1], drop_p, drop_site, drop_seed)
     if dgamma is not None:
         dgamma += (d * xh).sum(0)
     if dbeta is not None:
@@ -491,7 +499,7 @@ def ln_bwd(dy, v, stats, gamma, dv, M=None, add=None, dgamma=None, dbeta=None, d
         g = g + dres[:M].float()
     dv[:M] = g.to(dv.dtype)
     if dv2 is not None:
-        dv2[:M] = g.to(dv2.dtype)
+        dv2[:M] = (g * _row_keep(M, v.shape[1], drop2_p, drop2_site, drop2_seed) if drop2_p > 0 else g).to(dv2.dtype)
 
 
 def _f32_at(ptr, n):

@@ -250,6 +250,39 @@ def test_a_float_for_an_int_is_refused_not_truncated(rec):
     assert not rec.calls
 
 
+def test_layernorm_operands_read_through_a_bare_pointer_are_checked(rec):
+    """gamma, beta, add and stats reach the LayerNorm kernels as bare pointers: read as contiguous, add at leading dimension H, stats as [M, 2].  A
+    strided view, another dtype, a table of another width or too few rows of stats are refused by the wrapper, not silently misread."""
+    t = rec.tensor
+    M, H = 16, 64
+    act, g, b, st = (lambda: t(M, H, dtype=BF)), t(H), t(H), t(M, 2)
+    bad_vec = [t(2 * H)[::2], t(H, dtype=BF), t(H // 2)]
+    bad_stats = [t(M, 4)[:, :2], t(M - 1, 2), t(2, M).t(), t(M, 2, dtype=BF), t(2 * M)]
+    bad_add = [t(4, 2 * H)[:, :H], t(4, H, dtype=BF), t(4, H // 2), t(4 * H), t(8, H)[::2]]
+    calls = []
+    for v in bad_vec:
+        calls += [lambda v=v: L.ln_fwd(act(), v, b, 1e-12, act(), st), lambda v=v: L.ln_fwd(act(), g, v, 1e-12, act(), st),
+                  lambda v=v: L.ln_fwd(act(), g, v, 1e-12, None, st, y8=act().view(U8)[:, :H], ys=t(M)),
+                  lambda v=v: L.ln_bwd(act(), act(), st, v, act()), lambda v=v: L.ln_fwd_sum(act(), act(), v, b, 1e-12, act(), st),
+                  lambda v=v: L.ln_fwd_sum(act(), act(), g, v, 1e-12, act(), st)]
+    for s_ in bad_stats:
+        calls += [lambda s_=s_: L.ln_fwd(act(), g, b, 1e-12, act(), s_), lambda s_=s_: L.ln_bwd(act(), act(), s_, g, act()),
+                  lambda s_=s_: L.ln_fwd_sum(act(), act(), g, b, 1e-12, act(), s_)]
+    for a in bad_add:
+        calls += [lambda a=a: L.ln_fwd(act(), g, b, 1e-12, act(), st, add=a), lambda a=a: L.ln_bwd(act(), act(), st, g, act(), add=a)]
+    calls.append(lambda: L.ln_fwd(act(), g, b, 1e-12, act(), t(M, 2), M=M + 1))          # M rows asked of stats that has fewer
+    for f in calls:
+        with pytest.raises(AssertionError):
+            f()
+    assert not rec.calls
+    rows, half = t(8, H)[2:6], t(2 * H)[H:]                                              # contiguous slices (a table's rows, a flat buffer's tail): accepted
+    rec.known.update((rows.data_ptr(), half.data_ptr()))
+    L.ln_fwd(act(), g, b, 1e-12, act(), st, add=rows)
+    L.ln_fwd(act(), g, b, 1e-12, act(), None)                                            # stats are optional in a4r_ln_fwd
+    L.ln_bwd(act(), act(), t(M + 3, 2), half, act(), M=M)
+    assert rec.calls == dict(a4r_ln_fwd=2, a4r_ln_bwd=1)
+
+
 def test_the_loaded_library_enforces_the_table():
     """The same on the real library's host-side queries (no GPU needed): lib() installed the table, so a float, a missing argument and a foreign struct
     raise instead of reaching the C code (a surplus argument ctypes lets through on a cdecl function: the recorder above counts them)."""
