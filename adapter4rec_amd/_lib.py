@@ -196,7 +196,8 @@ def lib():
         from ._lib_ce_bf16 import SCORE_CE_BF16_SIGNATURES            # (the bf16 cross-entropy head's exports: a table of their own, bottom of this file)
         from ._lib_candidates import CANDIDATES_SIGNATURES            # (eval and top-K within a candidate set: likewise)
         from ._lib_user_lists import USER_LISTS_SIGNATURES            # (top-K and rank within a list of each user's own: likewise)
-        tables = dict(SIGNATURES, **SCORE_CE_BF16_SIGNATURES, **CANDIDATES_SIGNATURES, **USER_LISTS_SIGNATURES)
+        from ._lib_eval_negatives import EVAL_NEGATIVES_SIGNATURES    # (the negatives of a sampled evaluation drawn on the device: likewise)
+        tables = dict(SIGNATURES, **SCORE_CE_BF16_SIGNATURES, **CANDIDATES_SIGNATURES, **USER_LISTS_SIGNATURES, **EVAL_NEGATIVES_SIGNATURES)
         missing = [name for name in tables if not hasattr(_lib, name)]
         if missing:                   # a build from before an entry point was added (additions keep the ABI number: no argument list changes)
             _lib = None
@@ -953,6 +954,10 @@ _CANDIDATES_NAMES = ('CANDIDATES_SIGNATURES', 'candidate_mask', 'eval_rank_cand'
 _USER_LISTS_NAMES = ('USER_LISTS_SIGNATURES', 'LIST_MAX', 'topk_lists', 'eval_rank_lists')
 
 
+# The negatives of a sampled evaluation drawn on the device: include/a4r_eval_negatives.h and _lib_eval_negatives.py, held the same way.
+_EVAL_NEGATIVES_NAMES = ('EVAL_NEGATIVES_SIGNATURES', 'EVAL_NEG_SITE', 'EVAL_NEG_MAX', 'eval_draw_negatives', 'eval_rank_sampled')
+
+
 def __getattr__(name):
     if name in _CE_BF16_NAMES:
         from . import _lib_ce_bf16
@@ -963,4 +968,7 @@ def __getattr__(name):
     if name in _USER_LISTS_NAMES:
         from . import _lib_user_lists
         return getattr(_lib_user_lists, name)
+    if name in _EVAL_NEGATIVES_NAMES:
+        from . import _lib_eval_negatives
+        return getattr(_lib_eval_negatives, name)
     raise AttributeError(f'module {__name__!r} has no attribute {name!r}')

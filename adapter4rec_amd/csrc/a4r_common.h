@@ -299,6 +299,8 @@ A4R_DEV uint64_t a4r_hash64(uint64_t seed, uint32_t site, uint64_t idx) {
 }
 // The hash's other user: a4r_id_sample draws a training batch's negatives from a4r_hash64(seed, A4R_SAMPLE_SITE, counter).  The dropout sites
 // are 999, 16 i + {0, 1, 2}, 4000 and 4096 + 16 j + {0, 1, 2} (engine.py): 7001 is none of them.
+// A third: the negatives of a sampled evaluation, a4r_hash64(seed, A4R_EVAL_NEG_SITE = 7002, counter) (include/a4r_eval_negatives.h) -- no dropout
+// site either, and not 7001.
 #define A4R_SAMPLE_SITE 7001u
 A4R_DEV bool dropout_keep(uint64_t seed, uint32_t site, uint64_t e, uint32_t thr16) {
     uint64_t h = a4r_hash64(seed, site, e >> 2);

@@ -43,6 +43,10 @@ def parse_args(argv=None):
     p.add_argument('--recommend_out', type=str, default=None)          # --mode recommend: output file (default <model_dir>/recommend_<load_ckpt_name>.tsv)
     p.add_argument('--candidate_items', type=str, default=None)        # --mode test / recommend: a file of item names, one per line -- rank and recommend among these items only
     p.add_argument('--candidate_lists', type=str, default=None)        # --mode test / recommend: a file of `user_name \t item_name item_name ...` lines -- rank and recommend within each user's own list
+    p.add_argument('--eval_negatives', type=int, default=0)            # --mode test / the per-epoch evaluation: rank each target among N negatives drawn on the device (0 = off: the whole catalogue; at most 4096)
+    p.add_argument('--eval_neg_sampling', type=str, default='uniform', choices=['uniform', 'pop'])      # pop: in proportion to an item's occurrences in the training sequences
+    p.add_argument('--eval_neg_seed', type=int, default=20240607)      # the seed of the draws: the same negatives in every epoch, batch size and world size
+    p.add_argument('--eval_negatives_out', type=str, default=None)     # --mode test: write the test split's drawn negatives as a --candidate_lists file
     p.add_argument('--label_screen', type=str, default='None')
     p.add_argument('--logging_num', type=int, default=8)
     p.add_argument('--testing_num', type=int, default=1)

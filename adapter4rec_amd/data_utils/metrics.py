@@ -224,9 +224,11 @@ def candidate_lists_csr(candidate_lists, uids):
     return ptr, flat, lens
 
 
-def _both_refused(candidates, candidate_lists):
+def _both_refused(candidates, candidate_lists, eval_negatives=None):
     if candidates is not None and candidate_lists is not None:
         raise ValueError('candidates (one set for all users) and candidate_lists (a list per user) cannot be combined: give one of them')
+    if eval_negatives is not None and (candidates is not None or candidate_lists is not None):
+        raise ValueError('eval_negatives (negatives drawn per user) cannot be combined with candidates or candidate_lists: give one of them')
 
 
 def read_candidate_lists(path, user_names, item_names):
@@ -272,13 +274,152 @@ def candidate_lists_from_args(args, behaviors_path, name2id, Log_file):
     return lists
 
 
-def eval_ranks(model, user_history, eval_seq, item_embeddings, test_batch_size, args, user_ids, candidates=None, candidate_lists=None):
+EVAL_NEG_SEED = 20240607          # --eval_neg_seed's default: one constant for every rank, epoch and run (a draw is keyed by the GLOBAL user id)
+
+
+class EvalNegatives:
+    """A sampled evaluation's spec: rank every target among ``n`` negatives drawn on the device from the items the user has not interacted with
+    (include/a4r_eval_negatives.h: the draw rule, a pure function of seed, user id, the user's history and target, and the weights).
+    ``counts`` None: uniform; else one occurrence count per table row ([N + 1], entry 0 -- the pad item -- ignored): an item is drawn in
+    proportion to its count, an item of count 0 never.  Draws are independent: an id drawn twice counts once, so fewer than ``n`` distinct
+    negatives may stand against a target.  The cumulative counts are built and uploaded once per (table size, device)."""
+
+    def __init__(self, n, seed=EVAL_NEG_SEED, counts=None):
+        self.n, self.seed = int(n), int(seed)
+        if not 1 <= self.n <= LIST_MAX:
+            raise ValueError(f'eval_negatives: n = {self.n} negatives outside 1 .. {LIST_MAX}')
+        if not 0 <= self.seed < 2 ** 64:
+            raise ValueError(f'eval_negatives: seed = {self.seed} outside 0 .. 2^64 - 1')
+        self.counts = None
+        if counts is not None:
+            c = np.asarray(counts.cpu() if isinstance(counts, torch.Tensor) else counts).reshape(-1)
+            if c.size < 2 or not np.issubdtype(c.dtype, np.integer) or (c[1:] < 0).any():
+                raise ValueError('eval_negatives: counts must be non-negative integers, one per table row (entry 0 = the pad item)')
+            self.counts = c.astype(np.int64)
+            self.counts[0] = 0
+        self._dev = {}
+        self.last_err = None          # eval_ranks: the error word of its last evaluation (users without a candidate), a pinned int32 [1]
+
+    def weights(self, n1, dev):
+        """-> (cdf int64 [n1] on ``dev`` or None, cnt int64 [n1] on ``dev`` or None, whether some user could be left without a candidate)"""
+        key = (int(n1), str(dev))
+        if key not in self._dev:
+            if self.counts is None:
+                self._dev[key] = (None, None, n1 - 1 <= L.EVAL_MAX_HISTORY + 1)
+            else:
+                if self.counts.size != n1:
+                    raise ValueError(f'eval_negatives: {self.counts.size} counts for a table of {n1} rows')
+                cdf = np.cumsum(self.counts, dtype=np.int64)
+                if float(self.counts.astype(np.float64).sum()) >= 2.0 ** 62:
+                    raise ValueError('eval_negatives: the counts sum to 2^62 or more')
+                top = np.sort(self.counts)[-(L.EVAL_MAX_HISTORY + 1):].sum()          # the most mass a history and a target can take out
+                self._dev[key] = (torch.from_numpy(cdf).to(dev), torch.from_numpy(self.counts).to(dev), int(cdf[-1]) - int(top) < 1)
+        return self._dev[key]
+
+
+def item_counts(users_train, item_num):
+    """--eval_neg_sampling pop: the occurrences of every item in the training sequences -> int64 [item_num + 1]"""
+    import itertools
+    flat = np.fromiter(itertools.chain.from_iterable(users_train.values()), dtype=np.int64)
+    return np.bincount(flat[(flat > 0) & (flat <= item_num)], minlength=item_num + 1).astype(np.int64)
+
+
+def check_eval_negatives_flag(args):
+    """--eval_negatives N (with --eval_neg_sampling / --eval_neg_seed) is honoured by --mode test and by the per-epoch evaluation of training;
+    it is refused under --mode recommend and beside --candidate_items / --candidate_lists (a user's drawn negatives are the restriction), and
+    --eval_negatives_out is --mode test's."""
+    n = int(getattr(args, 'eval_negatives', 0) or 0)
+    out = getattr(args, 'eval_negatives_out', None)
+    if n == 0:
+        if out:
+            raise ValueError('--eval_negatives_out needs --eval_negatives N')
+        return
+    if not 1 <= n <= LIST_MAX:
+        raise ValueError(f'--eval_negatives {n}: outside 1 .. {LIST_MAX}')
+    if args.mode == 'recommend':
+        raise ValueError('--eval_negatives is an evaluation protocol: it is not honoured by --mode recommend')
+    for flag in ('candidate_items', 'candidate_lists'):
+        if getattr(args, flag, None):
+            raise ValueError(f'--eval_negatives and --{flag} cannot be combined: the drawn negatives are the candidates '
+                             '(to replay a draw, write it with --eval_negatives_out and give the file to --candidate_lists alone)')
+    if out and 'test' not in args.mode:
+        raise ValueError(f'--eval_negatives_out is honoured by --mode test only, not by --mode {args.mode}')
+    if not 0 <= int(args.eval_neg_seed) < 2 ** 64:
+        raise ValueError(f'--eval_neg_seed {args.eval_neg_seed}: outside 0 .. 2^64 - 1')
+
+
+def eval_negatives_from_args(args, users_train, item_num, Log_file):
+    """The runners' --eval_negatives N -> an EvalNegatives, or None without the flag (then nothing changes)."""
+    n = int(getattr(args, 'eval_negatives', 0) or 0)
+    if n == 0:
+        return None
+    pop = args.eval_neg_sampling == 'pop'
+    spec = EvalNegatives(n, seed=args.eval_neg_seed, counts=item_counts(users_train, item_num) if pop else None)
+    Log_file.info(f'eval negatives: {n} per user, {args.eval_neg_sampling} sampling, seed {spec.seed}'
+                  + (f', {int((spec.counts > 0).sum())} of {item_num} items with a training occurrence' if pop else ''))
+    return spec
+
+
+def _negatives_valid(spec, P, uid, n1, dev):
+    """float [len(uid)]: 1 where the user has an item left to draw (m >= 1 in the draw rule).  Only a catalogue that a history can exhaust
+    (uniform: at most 265 items; weighted: all but the 265 heaviest items weigh nothing) is looked at user by user, on the device."""
+    _, cnt, possible = spec.weights(n1, dev)
+    uid = torch.as_tensor(np.asarray(uid, dtype=np.int64)).to(dev)
+    if not possible or uid.numel() == 0:
+        return torch.ones(uid.numel(), device=dev)
+    hp = P['hptr']
+    lens = hp[uid + 1] - hp[uid]
+    rows = torch.repeat_interleave(torch.arange(uid.numel(), device=dev), lens)
+    within = torch.arange(int(lens.sum()), device=dev) - torch.repeat_interleave(torch.cumsum(lens, 0) - lens, lens)
+    ids = torch.cat([P['hflat32'][hp[uid][rows] + within].long(), P['target'][uid].long()])
+    rows = torch.cat([rows, torch.arange(uid.numel(), device=dev)])
+    keep = (ids > 0) & (ids < n1)
+    pairs = torch.unique(rows[keep] * n1 + ids[keep])
+    w = torch.ones_like(pairs) if cnt is None else cnt[pairs % n1]
+    mass = torch.zeros(uid.numel(), dtype=torch.int64, device=dev).scatter_add_(0, pairs // n1, w)
+    total = n1 - 1 if cnt is None else int(cnt.sum().item())
+    return (total - mass >= 1).float()
+
+
+def write_eval_negatives(spec, user_history, eval_seq, n1, args, user_names, item_names, path, dev):
+    """--eval_negatives_out: the materialised draws of every user of ``eval_seq`` (a4r_eval_draw_negatives: the ids a4r_eval_rank_sampled ranks
+    against, bit for bit), one ``user_name \t item_name item_name ...`` line per user who has a candidate -- the --candidate_lists format, so the
+    file given to --candidate_lists alone replays the evaluation of this split."""
+    P = _prepare_eval_set(eval_seq, user_history, args.max_seq_len + 1, dev)
+    cdf, _, _ = spec.weights(n1, dev)
+    n_users = len(eval_seq)
+    step = int(os.environ.get('A4R_EVAL_USER_BATCH', 0)) or 8192
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    hptr_host = P['hptr_host']
+    written = 0
+    with open(path, 'w') as f:
+        for a in range(0, n_users, step):
+            b = min(a + step, n_users)
+            h0, h1 = int(hptr_host[a]), int(hptr_host[b])
+            out = torch.zeros(b - a, spec.n, dtype=torch.int32, device=dev)
+            L.eval_draw_negatives((P['hptr'][a:b + 1] - h0).to(torch.int32), P['hflat32'][h0:h1 + 1], P['target32'][a:b],
+                                  torch.arange(a, b, dtype=torch.int32, device=dev), cdf, spec.seed, n1, out, err)
+            ids = out.cpu().numpy()
+            for u in range(a, b):
+                if ids[u - a, 0] != 0:                             # (no candidate: all zeros, no line -- the user is left out of the means either way)
+                    f.write(user_names[u] + '\t' + ' '.join(item_names[int(i)] for i in ids[u - a]) + '\n')
+                    written += 1
+    if written + int(err.item()) != n_users:
+        raise RuntimeError(f'eval negatives: {written} users drawn and {int(err.item())} counted without a candidate, of {n_users}')
+    return written
+
+
+def eval_ranks(model, user_history, eval_seq, item_embeddings, test_batch_size, args, user_ids, candidates=None, candidate_lists=None,
+               eval_negatives=None):
     """Rank (1 = best) of each listed user's held-out target among all items not in the user's history.  ``candidates`` (candidate_mask's
     input): among the candidate items only -- for every listed user; a target that is no candidate gets the rank it would have if it were.
     ``candidate_lists`` (a mapping, or a sequence indexed by user id, from user to an iterable of item ids, at most LIST_MAX each): among the
     user's own listed items only (a4r_eval_rank_lists: a sampled evaluation's negatives); a user without a list gets rank 1, the target need
-    not be listed."""
-    _both_refused(candidates, candidate_lists)
+    not be listed.  ``eval_negatives`` (an EvalNegatives): among the negatives drawn for the user on the device (a4r_eval_rank_sampled: one
+    launch per batch draws, scores and ranks; the user's key is its id here, so the draws do not depend on the batch, the shard or the epoch); a
+    user without a candidate gets rank 1 and is counted in ``eval_negatives.last_err``, a pinned word filled by an asynchronous copy: read it
+    after the next synchronisation."""
+    _both_refused(candidates, candidate_lists, eval_negatives)
     inner = _inner(model, args)
     dev = next(model.parameters()).device
     emb = item_embeddings.to(dev).float().contiguous()
@@ -295,6 +436,9 @@ def eval_ranks(model, user_history, eval_seq, item_embeddings, test_batch_size, 
     if candidate_lists is not None:                               # the CSR of the users' own lists, uploaded once, sliced per batch
         lptr, lflat_np, llens = candidate_lists_csr(candidate_lists, uid_np)
         lflat = torch.from_numpy(lflat_np).to(dev)
+    if eval_negatives is not None:                                # the weights, uploaded once; one error word for the whole evaluation
+        neg_cdf, _, _ = eval_negatives.weights(emb.shape[0], dev)
+        neg_err = torch.zeros(1, dtype=torch.int32, device=dev)
     # SequentialDistributedSampler hands every rank a run of consecutive users (its tail repeats the last ones): a batch of CONSECUTIVE users is a
     # slice of every prepared tensor -- no gather, no host-device round trip for the history count
     runs = np.flatnonzero(np.diff(uid_np) != 1) + 1
@@ -316,7 +460,10 @@ def eval_ranks(model, user_history, eval_seq, item_embeddings, test_batch_size, 
                 ptr = (P['hptr'][a:b + 1] - h0).to(torch.int32)
                 hist = P['hflat32'][h0:h1 + 1]                 # (+ 1: the kernel's table is never empty; the store ends in one spare 0)
                 rank = torch.zeros(nb, dtype=torch.int32, device=dev)
-                if candidate_lists is not None:
+                if eval_negatives is not None:
+                    L.eval_rank_sampled(prec, emb, P['target32'][a:b], ptr, hist, torch.arange(a, b, dtype=torch.int32, device=dev), neg_cdf,
+                                        eval_negatives.seed, eval_negatives.n, rank, neg_err)
+                elif candidate_lists is not None:
                     l0, l1 = int(lptr[s0]), int(lptr[s0 + nb])
                     L.eval_rank_lists(prec, emb, P['target32'][a:b], torch.from_numpy((lptr[s0:s0 + nb + 1] - l0).astype(np.int32)).to(dev),
                                       lflat[l0:l1 + 1], int(llens[s0:s0 + nb].max()), ptr, hist, rank)
@@ -325,6 +472,10 @@ def eval_ranks(model, user_history, eval_seq, item_embeddings, test_batch_size, 
                 else:
                     L.eval_rank_cand(prec, emb, P['target32'][a:b], ptr, hist, cand, rank)
                 ranks.append(rank)
+    if eval_negatives is not None:                                # not waited for: the caller reads it after its own synchronisation
+        host = torch.zeros(1, dtype=torch.int32)
+        eval_negatives.last_err = (host.pin_memory() if dev.type == 'cuda' else host)
+        eval_negatives.last_err.copy_(neg_err, non_blocking=True)
     out = torch.cat(ranks)
     if not first.all():
         out = out[torch.from_numpy(np.cumsum(first) - 1).to(dev)]
@@ -332,12 +483,16 @@ def eval_ranks(model, user_history, eval_seq, item_embeddings, test_batch_size, 
 
 
 def eval_model(model, user_history, eval_seq, item_embeddings, test_batch_size, args, item_num, Log_file, v_or_t, local_rank, candidates=None,
-               candidate_lists=None):
+               candidate_lists=None, eval_negatives=None):
     """metrics.py:82-116.  Returns mean Hit@10 over all users (ranks are gathered over the data-parallel group).  ``candidates``
     (candidate_mask's input): every target is ranked among the candidate items only, and the means run over the users whose target is a
     candidate (cold-start and split evaluation); ValueError when there is no such user.  ``candidate_lists`` (eval_ranks'): every target is
-    ranked among the user's own listed items, and the means run over the users who have a list; ValueError when no user has one."""
-    _both_refused(candidates, candidate_lists)
+    ranked among the user's own listed items, and the means run over the users who have a list; ValueError when no user has one.
+    ``eval_negatives`` (an EvalNegatives): every target is ranked among the negatives drawn for its user on the device -- the sampled protocol of
+    the SASRec / IDRec papers -- and the means run over the users who had an item left to draw."""
+    _both_refused(candidates, candidate_lists, eval_negatives)
+    if eval_negatives is not None:
+        return _eval_model_negatives(model, user_history, eval_seq, item_embeddings, test_batch_size, args, Log_file, v_or_t, eval_negatives)
     if candidate_lists is not None:
         return _eval_model_lists(model, user_history, eval_seq, item_embeddings, test_batch_size, args, Log_file, v_or_t, candidate_lists)
     if candidates is not None:
@@ -398,6 +553,30 @@ def _eval_model_lists(model, user_history, eval_seq, item_embeddings, test_batch
     ranks = eval_ranks(model, user_history, eval_seq, item_embeddings, test_batch_size, args, user_ids, candidate_lists=candidate_lists).float()
     valid = torch.from_numpy(has_candidate_list(candidate_lists, user_ids).astype(np.float32)).to(dev)
     return _means_over_valid(ranks, valid, n_users, topK, world, Log_file, v_or_t, 'candidate_lists', 'has a candidate list')
+
+
+def _eval_model_negatives(model, user_history, eval_seq, item_embeddings, test_batch_size, args, Log_file, v_or_t, spec):
+    """eval_model on drawn negatives: as _eval_model_lists, the validity flag being "the user has an item left to draw" (computed from the
+    histories; the kernels' own count of such users, read after the synchronisation of the means, must agree)."""
+    world = dist.get_world_size() if dist.is_initialized() else 1
+    rank_id = dist.get_rank() if dist.is_initialized() else 0
+    n_users = len(eval_seq)
+    sampler = SequentialDistributedSampler(range(n_users), test_batch_size, rank=rank_id, num_replicas=world)
+    user_ids = sampler.indices()
+    model.eval()
+    topK = 10
+    dev = next(model.parameters()).device
+    Log_file.info(v_or_t + '_methods   {}'.format('\t'.join(['Hit{}'.format(topK), 'nDCG{}'.format(topK)])))
+    ranks = eval_ranks(model, user_history, eval_seq, item_embeddings, test_batch_size, args, user_ids, eval_negatives=spec).float()
+    P = _prepare_eval_set(eval_seq, user_history, args.max_seq_len + 1, dev)
+    valid = _negatives_valid(spec, P, user_ids, item_embeddings.shape[0], dev)
+    uid = np.asarray(user_ids, dtype=np.int64)
+    first = torch.from_numpy(np.concatenate([[True], np.diff(uid) != 0])).to(dev) if uid.size else torch.zeros(0, dtype=torch.bool, device=dev)
+    without = (1.0 - valid)[first].sum()                               # (the sampler's tail repeats the last user: counted once, as the kernel does)
+    hr = _means_over_valid(ranks, valid, n_users, topK, world, Log_file, v_or_t, 'eval_negatives', 'has an item left to draw')
+    if spec.last_err is not None and int(spec.last_err.item()) != int(without.item()):
+        raise RuntimeError(f'{v_or_t}: the kernels counted {int(spec.last_err.item())} users without a candidate, the histories give {int(without.item())}')
+    return hr
 
 
 def _means_over_valid(ranks, valid, n_users, topK, world, Log_file, v_or_t, label, what):

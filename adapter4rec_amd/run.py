@@ -18,7 +18,7 @@ from torch.utils.data import DataLoader
 
 from .data_utils import (BuildTrainDataset, eval_model, get_doc_input_bert, get_item_embeddings, read_behaviors,
                          read_news_bert)
-from .data_utils.metrics import (candidate_lists_from_args, candidate_mask, candidates_from_args, check_candidate_flag, read_candidate_lists, read_candidates,
+from .data_utils.metrics import (check_eval_negatives_flag, eval_negatives_from_args, write_eval_negatives, candidate_lists_from_args, candidate_mask, candidates_from_args, check_candidate_flag, read_candidate_lists, read_candidates,
                                  write_recommendations)
 from .data_utils.preprocess import read_behavior_names
 from .data_utils.dataset import DeviceTrainSampler
@@ -91,13 +91,15 @@ def build_model(args, item_num, use_modal, bert_model, local_rank, Log_file, mod
     return model.to(local_rank), start_epoch, ckpt2
 
 
-def run_eval_once(model, item_content, user_history, users_eval, batch_size, item_num, use_modal, mode, local_rank, args, Log_file, candidates=None, candidate_lists=None):
+def run_eval_once(model, item_content, user_history, users_eval, batch_size, item_num, use_modal, mode, local_rank, args, Log_file, candidates=None, candidate_lists=None, eval_negatives=None):
     t0 = time.time()
     Log_file.info('Validating...')
     emb = get_item_embeddings(model, item_content, batch_size, args, use_modal, local_rank)
     kw = {} if candidates is None else dict(candidates=candidates)      # --candidate_items: ranked among, and averaged over targets within, the candidate set
     if candidate_lists is not None:                                     # --candidate_lists: ranked within the user's own list, averaged over the users who have one
         kw = dict(candidate_lists=candidate_lists)
+    if eval_negatives is not None:                                      # --eval_negatives: ranked among negatives drawn on the device, averaged over the users who have a candidate
+        kw = dict(eval_negatives=eval_negatives)
     hit10 = eval_model(model, user_history, users_eval, emb, batch_size, args, item_num, Log_file, mode, local_rank, **kw)
     report_time_eval(t0, Log_file)
     return hit10
@@ -134,6 +136,8 @@ def train(args, use_modal, local_rank, Log_file, Log_screen, model_dir, start_ti
                 items, mask = dev_sampler.sample(ids[i:i + args.batch_size])
                 yield items.view(-1, args.max_seq_len + 1, 2, items.size(-1)), mask
     model = FlatDDP(model, device_ids=[local_rank], output_device=local_rank)
+    neg = eval_negatives_from_args(args, users_train, item_num, Log_file)
+    ekw = {} if neg is None else dict(eval_negatives=neg)             # --eval_negatives; without the flag the calls are the ones made before
     optimizer = optimizer_from_args(optimizer_groups(model, args), args)      # --optimizer / --weight_decay / --max_grad_norm; default: FusedAdam
     if ckpt2 is not None:
         optimizer.load_state_dict(ckpt2['optimizer'])
@@ -172,13 +176,13 @@ def train(args, use_modal, local_rank, Log_file, Log_screen, model_dir, start_ti
         if not need_break and any_rank(torch.isnan(loss)):                 # a NaN after the last log step of the epoch: the reference checks
             need_break = True                                          # every batch (run.py:601-603); never evaluate / save NaN weights
         if not need_break:
-            hit10 = run_eval_once(model, item_content, hist_valid, users_valid, 512, item_num, use_modal, 'valid', local_rank, args, Log_file)
+            hit10 = run_eval_once(model, item_content, hist_valid, users_valid, 512, item_num, use_modal, 'valid', local_rank, args, Log_file, **ekw)
             if hit10 > max_eval:
                 max_eval, max_epoch = hit10, now_epoch
             model.train()
             if max_eval > max_hit10 or max_hit10 == 0 or ep % 10 == 0:
                 max_hit10 = max(max_hit10, max_eval)
-                run_eval_once(model, item_content, hist_test, users_test, 512, item_num, use_modal, 'test', local_rank, args, Log_file)
+                run_eval_once(model, item_content, hist_test, users_test, 512, item_num, use_modal, 'test', local_rank, args, Log_file, **ekw)
                 if use_modal and dist.get_rank() == 0:
                     save_model(now_epoch, model, model_dir, optimizer, torch.get_rng_state(), torch.cuda.get_rng_state(), Log_file)
         next_t = report_time_train(batch_index, now_epoch, loss, next_t, start_time, Log_file)
@@ -193,7 +197,7 @@ def train(args, use_modal, local_rank, Log_file, Log_screen, model_dir, start_ti
 def test(args, use_modal, local_rank, Log_file, Log_screen, model_dir, start_time):
     tokenizer, bert_model = load_backbone(args, Log_file)
     before_id2dic, before_name2id = read_news_bert(os.path.join(args.root_data_dir, args.dataset, args.news), args, tokenizer)
-    item_num, id2dic, _, users_valid, users_test, hist_valid, hist_test = read_behaviors(
+    item_num, id2dic, users_train, users_valid, users_test, hist_valid, hist_test = read_behaviors(
         os.path.join(args.root_data_dir, args.dataset, args.behaviors), before_id2dic, before_name2id,
         args.max_seq_len, args.min_seq_len, Log_file)
     item_content = np.concatenate([x for x in get_doc_input_bert(id2dic, args) if x is not None], axis=1)
@@ -205,6 +209,15 @@ def test(args, use_modal, local_rank, Log_file, Log_screen, model_dir, start_tim
     lists = candidate_lists_from_args(args, os.path.join(args.root_data_dir, args.dataset, args.behaviors), before_name2id, Log_file)
     if lists is not None:                                              # --candidate_lists (never beside --candidate_items: main refuses the pair)
         kw = dict(candidate_lists=lists)
+    neg = eval_negatives_from_args(args, users_train, item_num, Log_file)
+    if neg is not None:                                                # --eval_negatives (never beside either candidate flag: main refuses the pair)
+        kw = dict(eval_negatives=neg)
+        if args.eval_negatives_out and dist.get_rank() == 0:
+            user_names, item_names = read_behavior_names(os.path.join(args.root_data_dir, args.dataset, args.behaviors), before_name2id,
+                                                         args.max_seq_len, args.min_seq_len)
+            k = write_eval_negatives(neg, hist_test, users_test, item_num + 1, args, user_names, item_names, args.eval_negatives_out,
+                                     next(model.parameters()).device)
+            Log_file.info(f'eval negatives: the draws of the test split for {k} users -> {args.eval_negatives_out}')
     run_eval_once(model, item_content, hist_valid, users_valid, 512, item_num, use_modal, 'valid', local_rank, args, Log_file, **kw)
     run_eval_once(model, item_content, hist_test, users_test, 512, item_num, use_modal, 'test', local_rank, args, Log_file, **kw)
 
@@ -242,6 +255,7 @@ def setup_seed(seed):
 def main(argv=None):
     args = parse_args(argv)
     check_candidate_flag(args)
+    check_eval_negatives_flag(args)
     local_rank = args.local_rank if args.local_rank >= 0 else int(os.environ.get('LOCAL_RANK', 0))
     torch.cuda.set_device(local_rank)
     dist.init_process_group(backend='nccl', init_method='env://')      # 'nccl' is RCCL on ROCm

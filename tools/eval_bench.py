@@ -1,9 +1,12 @@
 #!/usr/bin/env python
 """Throughput of the native evaluation (reference: Downstream/Text/data_utils/metrics.py:62-116).
 
-  python tools/eval_bench.py [--items 65536] [--users 32768] [--json out.json] [--candidates FRACTION]
+  python tools/eval_bench.py [--items 65536] [--users 32768] [--json out.json] [--candidates FRACTION] [--sampled N [N ...]]
 
 --candidates FRACTION runs the candidate-set leg instead (candidates_leg): a4r_eval_rank_cand beside a4r_eval_rank, kernels only.
+--sampled N [N ...] runs the sampled-evaluation leg instead (sampled_leg): a4r_eval_rank_sampled beside the two-launch composition
+(a4r_eval_draw_negatives + a4r_eval_rank_lists), the full sweep a4r_eval_rank and an eager torch path, kernels only; one JSON line per
+configuration, appended to --json (the numbers land in profiles/eval_negatives_bench.jsonl).
 
 Times, on one MI355X, with BERT-base + Houlsby weights (random init, as bench.py):
   * the item sweep `get_item_embeddings` (all N + 1 titles through the item encoder, forward only) in the eval dtypes
@@ -71,6 +74,81 @@ def candidates_leg(a, dev):
         json.dump(res, open(a.json, 'w'), indent=1)
 
 
+def sampled_leg(a, dev):
+    """--sampled N [N ...]: ranking every user's target among N negatives drawn on the device, E = 64 and 128, uniform and popularity sampling, on
+    random tables of items + 1 rows and histories of 20 ids.  Four ways, interleaved over ``rounds`` rounds after a warm-up of each, the minimum
+    of the rounds reported (device events around ``reps`` calls):
+      fused     a4r_eval_rank_sampled: one launch, nothing of size U x N in memory
+      two       a4r_eval_draw_negatives + a4r_eval_rank_lists: the draws materialised [U, N] and read back as a CSR -- the figure to beat
+      sweep     a4r_eval_rank: the rank among ALL items (another protocol: what the sampling saves or costs)
+      eager     torch: randint negatives (no exclusion, another stream of draws) + gather + einsum + compare
+    fused and two must give the same ranks: checked on every configuration before anything is timed."""
+    from adapter4rec_amd import _lib as L
+    N1, U, rounds, reps = a.items + 1, a.users, 5, 5
+    g = torch.Generator(device=dev).manual_seed(B.SEED)
+    box = torch.cuda.get_device_name(0)
+    out = open(a.json, 'a') if a.json else None
+    for E in (64, 128):
+        emb = torch.randn(N1, E, device=dev, generator=g)
+        prec = torch.randn(U, E, device=dev, generator=g)
+        target = torch.randint(1, N1, (U,), device=dev, dtype=torch.int32, generator=g)
+        ptr = torch.arange(0, U + 1, device=dev, dtype=torch.int32) * 20
+        hidx = torch.randint(1, N1, (U * 20 + 1,), device=dev, dtype=torch.int32, generator=g)
+        keys = torch.arange(U, device=dev, dtype=torch.int32)
+        cnt = torch.randint(0, 1000, (N1,), device=dev, generator=g) ** 2 // 1000          # a skewed popularity, a tenth of the items near 0
+        cnt[0] = 0
+        pop_cdf = torch.cumsum(cnt, 0).to(torch.int64).contiguous()
+        rank = torch.zeros(U, dtype=torch.int32, device=dev)
+        rank2 = torch.zeros(U, dtype=torch.int32, device=dev)
+        err = torch.zeros(1, dtype=torch.int32, device=dev)
+        for n in a.sampled:
+            ids = torch.zeros(U, n, dtype=torch.int32, device=dev)
+            lptr = torch.arange(0, U + 1, device=dev, dtype=torch.int32) * n
+            for sampling, cdf in (('uniform', None), ('pop', pop_cdf)):
+                def fused():
+                    L.eval_rank_sampled(prec, emb, target, ptr, hidx, keys, cdf, B.SEED, n, rank, err)
+
+                def two():
+                    L.eval_draw_negatives(ptr, hidx, target, keys, cdf, B.SEED, N1, ids, err)
+                    L.eval_rank_lists(prec, emb, target, lptr, ids.view(-1), n, ptr, hidx, rank2)
+
+                def sweep():
+                    L.eval_rank(prec, emb, target, ptr, hidx, rank2)
+
+                def eager():
+                    neg = torch.randint(1, N1, (U, n), device=dev)
+                    s = torch.einsum('ue,une->un', prec, emb[neg])
+                    t = (prec * emb[target.long()]).sum(1, keepdim=True)
+                    return 1 + (s > t).sum(1)
+                fused()
+                two()
+                torch.cuda.synchronize()
+                assert torch.equal(rank, rank2) and int(err.item()) == 0, 'the fused entry and the two-launch composition disagree'
+                legs = dict(fused=fused, two=two, sweep=sweep, eager=eager)
+                us = {k: [] for k in legs}
+                for fn in legs.values():
+                    fn()
+                    fn()
+                for _ in range(rounds):
+                    for k, fn in legs.items():
+                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        e0.record()
+                        for _ in range(reps):
+                            fn()
+                        e1.record()
+                        torch.cuda.synchronize()
+                        us[k].append(round(e0.elapsed_time(e1) / reps * 1e3, 1))
+                best = {k: min(v) for k, v in us.items()}
+                line = dict(box=box, items=N1, users=U, E=E, N=n, sampling=sampling, rounds=rounds, reps=reps,
+                            fused_us=best['fused'], two_launch_us=best['two'], sweep_us=best['sweep'], eager_us=best['eager'], all_us=us,
+                            fused_over_two_launch=round(best['fused'] / best['two'], 3), fused_users_per_s=round(U / best['fused'] * 1e6, 1),
+                            gathered_GB_per_s=round(U * (n + 1) * E * 4 / best['fused'] / 1e3, 1), mean_rank=round(float(rank.float().mean()), 2))
+                print(json.dumps(line), flush=True)
+                if out:
+                    out.write(json.dumps(line) + '\n')
+                    out.flush()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--items', type=int, default=65536)
@@ -78,11 +156,15 @@ def main():
     ap.add_argument('--json', default='')
     ap.add_argument('--candidates', type=float, default=None, metavar='FRACTION',
                     help='run the candidate-set leg instead: a4r_eval_rank_cand beside a4r_eval_rank under a random mask of this fraction')
+    ap.add_argument('--sampled', type=int, nargs='+', default=None, metavar='N',
+                    help='run the sampled-evaluation leg instead: a4r_eval_rank_sampled beside draw + rank_lists, the full sweep and eager torch, at N negatives')
     a = ap.parse_args()
     dev = torch.device('cuda', 0)
     torch.cuda.set_device(0)
     if a.candidates is not None:
         return candidates_leg(a, dev)
+    if a.sampled is not None:
+        return sampled_leg(a, dev)
     from adapter4rec_amd import _lib as L
     from adapter4rec_amd.data_utils import eval_model, get_item_embeddings
     args = B.make_args(32, 'bf16')
