@@ -197,7 +197,9 @@ def lib():
         from ._lib_candidates import CANDIDATES_SIGNATURES            # (eval and top-K within a candidate set: likewise)
         from ._lib_user_lists import USER_LISTS_SIGNATURES            # (top-K and rank within a list of each user's own: likewise)
         from ._lib_eval_negatives import EVAL_NEGATIVES_SIGNATURES    # (the negatives of a sampled evaluation drawn on the device: likewise)
-        tables = dict(SIGNATURES, **SCORE_CE_BF16_SIGNATURES, **CANDIDATES_SIGNATURES, **USER_LISTS_SIGNATURES, **EVAL_NEGATIVES_SIGNATURES)
+        from ._lib_diversify import DIVERSIFY_SIGNATURES                # (the diversified re-ranking of a top-K list: likewise)
+        tables = dict(SIGNATURES, **SCORE_CE_BF16_SIGNATURES, **CANDIDATES_SIGNATURES, **USER_LISTS_SIGNATURES, **EVAL_NEGATIVES_SIGNATURES,
+                      **DIVERSIFY_SIGNATURES)
         missing = [name for name in tables if not hasattr(_lib, name)]
         if missing:                   # a build from before an entry point was added (additions keep the ABI number: no argument list changes)
             _lib = None
@@ -958,6 +960,10 @@ _USER_LISTS_NAMES = ('USER_LISTS_SIGNATURES', 'LIST_MAX', 'topk_lists', 'eval_ra
 _EVAL_NEGATIVES_NAMES = ('EVAL_NEGATIVES_SIGNATURES', 'EVAL_NEG_SITE', 'EVAL_NEG_MAX', 'eval_draw_negatives', 'eval_rank_sampled')
 
 
+# The diversified re-ranking of a top-K list: include/a4r_diversify.h and _lib_diversify.py, held the same way.
+_DIVERSIFY_NAMES = ('DIVERSIFY_SIGNATURES', 'MMR_MAX_POOL', 'mmr_rerank')
+
+
 def __getattr__(name):
     if name in _CE_BF16_NAMES:
         from . import _lib_ce_bf16
@@ -971,4 +977,7 @@ def __getattr__(name):
     if name in _EVAL_NEGATIVES_NAMES:
         from . import _lib_eval_negatives
         return getattr(_lib_eval_negatives, name)
+    if name in _DIVERSIFY_NAMES:
+        from . import _lib_diversify
+        return getattr(_lib_diversify, name)
     raise AttributeError(f'module {__name__!r} has no attribute {name!r}')

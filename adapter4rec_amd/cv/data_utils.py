@@ -8,7 +8,7 @@ import numpy as np
 import torch
 
 from ..data_utils.metrics import _gather_shards, _inner, _my_shard, eval_model, eval_ranks       # noqa: F401
-from ..data_utils.metrics import candidate_mask, read_candidate_lists, read_candidates, recommend, write_recommendations       # noqa: F401
+from ..data_utils.metrics import Diversify, candidate_mask, read_candidate_lists, read_candidates, recommend, write_recommendations       # noqa: F401
 from .image_io import RecordStore, decode_record, resize_to_square
 
 

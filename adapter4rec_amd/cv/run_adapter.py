@@ -23,7 +23,7 @@ from ..inject import freeze_all
 from ..optim import from_args as optimizer_from_args
 from . import Model, ModelCPC, ViTForImageClassification, ViTMAEModel
 from .data_utils import eval_model, get_itemId_embeddings, get_itemLMDB_embeddings, open_image_db, read_behaviors, read_images
-from ..data_utils.metrics import (check_eval_negatives_flag, eval_negatives_from_args, write_eval_negatives, candidate_lists_from_args, candidate_mask, candidates_from_args, check_candidate_flag, read_candidate_lists, read_candidates,
+from ..data_utils.metrics import (check_eval_negatives_flag, eval_negatives_from_args, write_eval_negatives, candidate_lists_from_args, candidate_mask, candidates_from_args, check_candidate_flag, check_diversify_flag, diversify_from_args, read_candidate_lists, read_candidates,
                                   write_recommendations)
 from ..data_utils.preprocess import read_behavior_names
 from .image_io import Build_Lmdb_Dataset, assemble_batch, collate_host
@@ -285,7 +285,8 @@ def recommend(args, use_modal, local_rank, Log_file, Log_screen, model_dir, star
     out = args.recommend_out or os.path.join(model_dir, f'recommend_{args.load_ckpt_name}.tsv')
     out = write_recommendations(model, users_test, hist_test, emb, args.topk, 256, args, user_names, item_names, out,
                                 candidates=read_candidates(args.candidate_items, item_names) if args.candidate_items else None,
-                                candidate_lists=read_candidate_lists(args.candidate_lists, user_names, item_names) if args.candidate_lists else None)
+                                candidate_lists=read_candidate_lists(args.candidate_lists, user_names, item_names) if args.candidate_lists else None,
+                                diversify=diversify_from_args(args, Log_file), Log_file=Log_file)
     if out:
         Log_file.info(f'recommend: top-{args.topk} lists of {len(users_test)} users -> {out}')
 
@@ -294,6 +295,7 @@ def main(argv=None):
     args = parse_args(argv)
     check_candidate_flag(args)
     check_eval_negatives_flag(args)
+    check_diversify_flag(args)
     local_rank = args.local_rank if args.local_rank >= 0 else int(os.environ.get('LOCAL_RANK', 0))
     torch.cuda.set_device(local_rank)
     dist.init_process_group(backend='nccl', init_method='env://')      # 'nccl' is RCCL on ROCm

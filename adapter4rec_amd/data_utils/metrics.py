@@ -14,6 +14,7 @@ import torch.distributed as dist
 
 from .. import _lib as L
 from .._lib_user_lists import LIST_MAX
+from .._lib_diversify import MMR_MAX_POOL
 from .dataset import SequentialDistributedSampler
 
 
@@ -178,6 +179,43 @@ def check_candidate_flag(args):
                              '(training and its per-epoch evaluation range over the whole catalogue)')
     if getattr(args, 'candidate_items', None) and getattr(args, 'candidate_lists', None):
         raise ValueError('--candidate_lists (a list per user) and --candidate_items (one set for all users) cannot be combined: give one of them')
+
+
+class Diversify:
+    """recommend's ``diversify``: re-rank each user's ``pool`` best items by maximal marginal relevance (a4r_mmr_rerank; the rule is in
+    include/a4r_diversify.h) -- k greedy picks by ``lam`` * relevance - (1 - ``lam``) * (largest cosine to an item already picked), relevance the
+    score scaled to [0, 1] over the pool.  ``lam`` = 1 is the plain list; ``pool`` (at most MMR_MAX_POOL = 256) bounds how far down the ranking a
+    pick can come from."""
+
+    def __init__(self, lam=0.7, pool=100):
+        self.lam, self.pool = float(lam), int(pool)
+        if math.isnan(self.lam) or not 0.0 <= self.lam <= 1.0:
+            raise ValueError(f'diversify: lambda = {self.lam} outside [0, 1]')
+        if not 1 <= self.pool <= MMR_MAX_POOL:
+            raise ValueError(f'diversify: pool = {self.pool} outside 1 .. {MMR_MAX_POOL}')
+
+
+def check_diversify_flag(args):
+    """--diversify mmr (with --mmr_lambda / --mmr_pool) re-ranks the lists of --mode recommend; every other mode refuses it instead of ignoring
+    it.  The pool is a top-K output that the --topk list is cut from: topk <= pool <= 256."""
+    if getattr(args, 'diversify', 'none') == 'none':
+        return
+    if args.mode != 'recommend':
+        raise ValueError(f'--diversify {args.diversify} is honoured by --mode recommend only, not by --mode {args.mode}')
+    lam = float(args.mmr_lambda)
+    if math.isnan(lam) or not 0.0 <= lam <= 1.0:
+        raise ValueError(f'--mmr_lambda {args.mmr_lambda}: outside [0, 1]')
+    if not int(args.topk) <= int(args.mmr_pool) <= MMR_MAX_POOL:
+        raise ValueError(f'--mmr_pool {args.mmr_pool}: outside --topk = {args.topk} .. {MMR_MAX_POOL}')
+
+
+def diversify_from_args(args, Log_file):
+    """The runners' --diversify mmr -> a Diversify, or None without the flag (then nothing changes)."""
+    if getattr(args, 'diversify', 'none') == 'none':
+        return None
+    spec = Diversify(args.mmr_lambda, args.mmr_pool)
+    Log_file.info(f'diversify: mmr, lambda {spec.lam:g}, pool {spec.pool}')
+    return spec
 
 
 def candidates_from_args(args, behaviors_path, name2id, Log_file):
@@ -626,7 +664,7 @@ def _recommend_inputs(user_seqs, exclude, uids, T):
     return ids, mask, ptr, flat
 
 
-def recommend(model, user_seqs, item_embeddings, k, args, exclude=None, user_ids=None, candidates=None, candidate_lists=None):
+def recommend(model, user_seqs, item_embeddings, k, args, exclude=None, user_ids=None, candidates=None, candidate_lists=None, diversify=None):
     """The k best items for each listed user (default: every user of ``user_seqs``), after the user's sequence.
 
     ``user_seqs[u]``: the user's item ids (1 .. N); its last ``max_seq_len`` items go through ``user_encoder``, left-padded as an evaluation
@@ -638,8 +676,19 @@ def recommend(model, user_seqs, item_embeddings, k, args, exclude=None, user_ids
     is never formed).  ``candidates`` (candidate_mask's input: bool / uint8 [N + 1], one set for all users): the lists are drawn from the
     candidate items only (a4r_topk_items_cand) -- the catalogue in stock, say, which no 264-id exclusion list could express.
     ``candidate_lists`` (eval_ranks': user -> an iterable of item ids, at most LIST_MAX each, longer lists raise ``ValueError``): the k best of
-    the user's own listed items (a4r_topk_lists) -- a retrieval stage's shortlist, re-ranked; a user without a list gets pad slots only."""
+    the user's own listed items (a4r_topk_lists) -- a retrieval stage's shortlist, re-ranked; a user without a list gets pad slots only.
+    ``diversify`` (a Diversify; k <= its pool): the entry above fills a pool of ``diversify.pool`` items per user instead, and a4r_mmr_rerank picks
+    the k of them to return -- near-duplicates of an item already in the list give way to other items.  The scores are still the relevance
+    scores, in pick order: they need not descend."""
+    return _recommend(model, user_seqs, item_embeddings, k, args, exclude, user_ids, candidates, candidate_lists, diversify, False)[:2]
+
+
+def _recommend(model, user_seqs, item_embeddings, k, args, exclude, user_ids, candidates, candidate_lists, diversify, want_ild):
+    """recommend's body -> (ids, scores, ild): ild None unless ``want_ild`` under ``diversify``, then fp32 [U, 2] = the intra-list diversity (mean
+    1 - cosine over a list's pairs of items) of the plain top-k list and of the re-ranked one, both from the one pool."""
     _both_refused(candidates, candidate_lists)
+    if diversify is not None and not 1 <= int(k) <= diversify.pool:
+        raise ValueError(f'diversify: k = {int(k)} outside 1 .. pool = {diversify.pool}')
     inner = _inner(model, args)
     dev = next(model.parameters()).device
     emb = item_embeddings.to(dev).float().contiguous()
@@ -648,15 +697,18 @@ def recommend(model, user_seqs, item_embeddings, k, args, exclude=None, user_ids
     k = int(k)
     cand = candidate_mask(candidates, emb.shape[0], dev)
     uids = np.arange(len(user_seqs), dtype=np.int64) if user_ids is None else np.asarray(user_ids, dtype=np.int64).reshape(-1)
+    want_ild = want_ild and diversify is not None
     if uids.size == 0:
-        return torch.zeros(0, k, dtype=torch.long, device=dev), torch.zeros(0, k, dtype=torch.float32, device=dev)
+        return (torch.zeros(0, k, dtype=torch.long, device=dev), torch.zeros(0, k, dtype=torch.float32, device=dev),
+                torch.zeros(0, 2, dtype=torch.float32, device=dev) if want_ild else None)
+    kk = k if diversify is None else diversify.pool                # what the top-K entry is asked for
     ids_np, mask_np, ptr_np, flat_np = _recommend_inputs(user_seqs, exclude, uids, T)
     step = int(os.environ.get('A4R_EVAL_USER_BATCH', 0)) or 8192          # (eval_ranks' user batch)
     flat = torch.from_numpy(flat_np).to(dev)
     if candidate_lists is not None:                               # the CSR of the users' own lists, uploaded once, sliced per batch
         lptr, lflat_np, llens = candidate_lists_csr(candidate_lists, uids)
         lflat = torch.from_numpy(lflat_np).to(dev)
-    out_ids, out_scores = [], []
+    out_ids, out_scores, out_ild = [], [], []
     model.eval()
     with torch.no_grad():
         for a in range(0, uids.size, step):
@@ -667,28 +719,41 @@ def recommend(model, user_seqs, item_embeddings, k, args, exclude=None, user_ids
             prec = inner.user_encoder(input_embs, torch.from_numpy(mask_np[a:b]).to(dev), None)[:, -1].contiguous()
             h0, h1 = int(ptr_np[a]), int(ptr_np[b])
             ptr = torch.from_numpy((ptr_np[a:b + 1] - h0).astype(np.int32)).to(dev)
-            ids = torch.empty(nb, k, dtype=torch.int32, device=dev)
-            scores = torch.empty(nb, k, dtype=torch.float32, device=dev)
+            ids = torch.empty(nb, kk, dtype=torch.int32, device=dev)
+            scores = torch.empty(nb, kk, dtype=torch.float32, device=dev)
             if candidate_lists is not None:
                 l0, l1 = int(lptr[a]), int(lptr[b])
                 L.topk_lists(prec, emb, torch.from_numpy((lptr[a:b + 1] - l0).astype(np.int32)).to(dev), lflat[l0:l1 + 1], int(llens[a:b].max()),
-                             ptr, flat[h0:h1 + 1], k, ids, scores)
+                             ptr, flat[h0:h1 + 1], kk, ids, scores)
             elif cand is None:
-                L.topk_items(prec, emb, ptr, flat[h0:h1 + 1], k, ids, scores)
+                L.topk_items(prec, emb, ptr, flat[h0:h1 + 1], kk, ids, scores)
             else:
-                L.topk_items_cand(prec, emb, ptr, flat[h0:h1 + 1], cand, k, ids, scores)
+                L.topk_items_cand(prec, emb, ptr, flat[h0:h1 + 1], cand, kk, ids, scores)
+            if diversify is not None:                                 # ids / scores are the pool: cut it to k
+                pool_ids, pool_scores = ids, scores
+                ids = torch.empty(nb, k, dtype=torch.int32, device=dev)
+                scores = torch.empty(nb, k, dtype=torch.float32, device=dev)
+                ild = torch.empty(2, nb, dtype=torch.float32, device=dev) if want_ild else None                      # the plain list's, the re-ranked one's
+                if want_ild:                                          # lambda = 1: the plain top-k list, for its diversity alone
+                    L.mmr_rerank(emb, pool_ids, pool_scores, 1.0, k, ids, scores, ild[0])
+                L.mmr_rerank(emb, pool_ids, pool_scores, diversify.lam, k, ids, scores, ild[1] if want_ild else None)
+                if want_ild:
+                    out_ild.append(ild.t())
             out_ids.append(ids.long())
             out_scores.append(scores)
-    return torch.cat(out_ids), torch.cat(out_scores)
+    return torch.cat(out_ids), torch.cat(out_scores), (torch.cat(out_ild).contiguous() if want_ild else None)
 
 
 def write_recommendations(model, user_seqs, user_history, item_embeddings, k, batch_size, args, user_names, item_names, path, candidates=None,
-                          candidate_lists=None):
+                          candidate_lists=None, diversify=None, Log_file=None):
     """The runners' --mode recommend: the k next items after every user's whole known sequence (``user_seqs[u]``, the evaluation input of the
     test split, whose last item is the held-out one), excluding ``user_history[u]`` plus that last item -- everything the user is known to have
     seen.  Users are sharded over the data-parallel ranks as eval_model shards them; rank 0 writes ``path``: one line per user, in uid order,
     ``user_name \\t item_1 ... item_k \\t score_1 ... score_k`` with the item file's names (pad slots of a short list omitted).
-    ``candidates``, ``candidate_lists``: as recommend's; under ``candidate_lists`` a user without a list gets no line."""
+    ``candidates``, ``candidate_lists``: as recommend's; under ``candidate_lists`` a user without a list gets no line.
+    ``diversify``: as recommend's.  The file's format is unchanged; a line's scores are the items' relevance scores in the order the items were
+    picked, no longer necessarily descending.  ``Log_file`` then gets one line, ``recommend_ild``: the mean intra-list diversity (mean 1 - cosine
+    over a list's pairs of items) of the plain top-k lists and of the re-ranked ones, over the users with at least two items (``k of n users``)."""
     world = dist.get_world_size() if dist.is_initialized() else 1
     rank_id = dist.get_rank() if dist.is_initialized() else 0
     n_users = len(user_seqs)
@@ -698,17 +763,26 @@ def write_recommendations(model, user_seqs, user_history, item_embeddings, k, ba
         u = int(u)
         if u not in exclude:
             exclude[u] = np.concatenate([np.asarray(user_history[u], dtype=np.int64).reshape(-1), np.asarray(user_seqs[u][-1:], dtype=np.int64)])
-    ids, scores = recommend(model, user_seqs, item_embeddings, k, args, exclude=exclude, user_ids=uids, candidates=candidates,
-                            candidate_lists=candidate_lists)
+    ids, scores, ild = _recommend(model, user_seqs, item_embeddings, k, args, exclude, uids, candidates, candidate_lists, diversify, True)
     if world > 1:
         parts_i = [torch.zeros_like(ids) for _ in range(world)]
         parts_s = [torch.zeros_like(scores) for _ in range(world)]
         dist.all_gather(parts_i, ids)
         dist.all_gather(parts_s, scores)
         ids, scores = torch.cat(parts_i), torch.cat(parts_s)
+        if ild is not None:                                        # gathered over the ranks the way the ids are
+            parts_d = [torch.zeros_like(ild) for _ in range(world)]
+            dist.all_gather(parts_d, ild)
+            ild = torch.cat(parts_d)
     if rank_id != 0:
         return None
     ids, scores = ids[:n_users].cpu().numpy(), scores[:n_users].cpu().numpy()
+    if ild is not None and Log_file is not None:
+        pairs = (ids != 0).sum(1) >= 2                             # a list of fewer than two items has no diversity to speak of
+        d = ild[:n_users].cpu().numpy().astype(np.float64)[pairs]
+        plain, mmr = (float(d[:, 0].mean()), float(d[:, 1].mean())) if d.shape[0] else (0.0, 0.0)
+        Log_file.info('recommend_ild   top-{} {:0.5f}   mmr(lambda {:g}, pool {}) {:0.5f}   {} of {} users'.format(
+            k, plain, diversify.lam, diversify.pool, mmr, int(pairs.sum()), n_users))
     listed = np.ones(n_users, bool) if candidate_lists is None else has_candidate_list(candidate_lists, range(n_users))
     with open(path, 'w') as f:
         for u in range(n_users):

@@ -2,12 +2,14 @@
 """Top-K recommendation on one MI355X: a4r_topk_items beside a4r_eval_rank (the same scoring sweep, one rank per user) and beside the torch path a
 user would otherwise write (chunked fp32 matmul, history masked, torch.topk), and recommend() end to end -- one JSON line per configuration.
 
-    python tools/topk_bench.py [--iters N] [--only NAME] [--candidates FRACTION] [--lists C]
+    python tools/topk_bench.py [--iters N] [--only NAME] [--candidates FRACTION] [--lists C] [--mmr]
 
 --candidates FRACTION runs the candidate-set leg instead (cand_cfg): a4r_topk_items_cand / a4r_eval_rank_cand beside the unmasked entries, interleaved.
 --lists C runs the per-user-list leg instead (lists_cfg): a4r_topk_lists over C listed items per user (C = 0: 100, 1000 and 4096 in turn), E = 64 and
 128, beside the eager path a caller without the kernel writes (chunked emb[idx] gather, einsum, exclusion mask, torch.topk), interleaved, and beside
 a4r_topk_items over the whole table for scale.
+--mmr runs the re-ranking leg instead (mmr_cfg): a4r_mmr_rerank cutting a4r_topk_items' pools of 100 and 256 items to 10, E = 64 and 128, lambda 0.7,
+beside the eager composition on the same pools (gather, bmm cosine matrix, a K-round loop from the host), interleaved.
 
 Shapes: 32 768 users x 65 537 items (the evaluation benchmark's shape) and x 500 001 items (the ID tower's 500 000-item table), E = 64, K 10 / 100,
 histories of 20 uniform ids.  Kernel times are HIP-event means over N launches after a warm-up; per-kernel times: run this under
@@ -147,6 +149,66 @@ def lists_cfg(name, U, N1, E, k, C, iters, rounds=2, H=20):
                 gather_GBps=round(U * C * E * 4 / best / 1e6, 1), topk_items_whole_table_ms=round(t_table, 4), id_agreement_with_eager=round(agree, 6))
 
 
+def eager_mmr(emb, pool_ids, pool_scores, lam, k, chunk):
+    """what a caller without the kernel writes: gather the pool's rows of a chunk of users, normalise them, one bmm for the [chunk, P, P] cosine
+    matrix, then k rounds of masked argmax and a running maximum over the picked column, driven from the host"""
+    ids, scores = [], []
+    P = pool_ids.shape[1]
+    for a in range(0, pool_ids.shape[0], chunk):
+        pid, ps = pool_ids[a:a + chunk].long(), pool_scores[a:a + chunk]
+        free = (pid > 0) & torch.isfinite(ps)
+        rows = emb[pid]
+        rows = rows / rows.norm(dim=2, keepdim=True).clamp_min(1e-30)
+        G = torch.bmm(rows, rows.transpose(1, 2))
+        lo = torch.where(free, ps, ps.new_full((), float('inf'))).amin(1, keepdim=True)
+        hi = torch.where(free, ps, ps.new_full((), -float('inf'))).amax(1, keepdim=True)
+        r = torch.where(hi > lo, (ps - lo) / (hi - lo), torch.ones_like(ps))
+        m = torch.zeros_like(ps)
+        oi = torch.zeros(pid.shape[0], k, dtype=torch.long, device=pid.device)
+        os_ = torch.full((pid.shape[0], k), -float('inf'), device=pid.device)
+        for t in range(k):
+            v = (lam * r - (1.0 - lam) * m).masked_fill(~free, -float('inf'))
+            j = v.argmax(1, keepdim=True)
+            ok = free.gather(1, j)
+            oi[:, t:t + 1] = torch.where(ok, pid.gather(1, j), 0)
+            os_[:, t:t + 1] = torch.where(ok, ps.gather(1, j), -float('inf'))
+            free.scatter_(1, j, False)
+            c = G.gather(1, j[:, :, None].expand(-1, 1, P)).squeeze(1)
+            m = c if t == 0 else torch.maximum(m, c)
+        ids.append(oi)
+        scores.append(os_)
+    return torch.cat(ids), torch.cat(scores)
+
+
+def mmr_cfg(name, U, N1, E, k, P, lam, iters, rounds=2, H=20):
+    """--mmr: the pools are a4r_topk_items' P best items of every user; a4r_mmr_rerank and the eager composition on the same pools, interleaved
+    `rounds` times, every round's mean reported, the ratio from the minima; a4r_topk_items at K = P, which fills the pool, once for scale."""
+    from adapter4rec_amd import _lib as L
+    emb, prec, hist, ptr, tgt = data(U, N1, E, H)
+    flat = hist.reshape(-1).contiguous()
+    pool_i = torch.empty(U, P, dtype=torch.int32, device=DEV)
+    pool_s = torch.empty(U, P, dtype=torch.float32, device=DEV)
+    t_pool = timed(lambda: L.topk_items(prec, emb, ptr, flat, P, pool_i, pool_s), max(1, iters // 4))
+    ids = torch.empty(U, k, dtype=torch.int32, device=DEV)
+    sc = torch.empty(U, k, dtype=torch.float32, device=DEV)
+    ild = torch.empty(U, dtype=torch.float32, device=DEV)
+    chunk = max(1, (1 << 28) // (P * max(P, E)))                    # 1 GiB of gathered rows or of cosine matrix per chunk
+    legs = dict(mmr_rerank=lambda: L.mmr_rerank(emb, pool_i, pool_s, lam, k, ids, sc, ild), eager=lambda: eager_mmr(emb, pool_i, pool_s, lam, k, chunk))
+    ms = {n: [] for n in legs}
+    for _ in range(rounds):
+        for n, fn in legs.items():
+            ms[n].append(round(timed(fn, iters if n == 'mmr_rerank' else max(1, iters // 4)), 4))
+    ei, _ = eager_mmr(emb, pool_i, pool_s, lam, k, chunk)
+    legs['mmr_rerank']()
+    agree = float((ei.int() == ids).all(1).float().mean())          # random fp32 data: the lists agree up to near-ties
+    changed = float((ids != pool_i[:, :k]).any(1).float().mean())
+    best = min(ms['mmr_rerank'])
+    return dict(name=name, users=U, items=N1, E=E, k=k, pool=P, lam=lam, rounds=rounds, iters=iters, **{n + '_ms': v for n, v in ms.items()},
+                eager_over_mmr_rerank=round(min(ms['eager']) / best, 2), users_per_s=round(U / best * 1e3),
+                row_read_GBps=round(U * k * P * E * 4 / best / 1e6, 1), topk_items_pool_ms=round(t_pool, 4), mean_ild=round(float(ild.mean()), 5),
+                lists_equal_to_eager=round(agree, 6), lists_changed_by_mmr=round(changed, 4))
+
+
 def recommend_cfg(name, U, item_num, k, iters, T=20):
     from adapter4rec_amd.cv import Model
     from adapter4rec_amd.cv.data_utils import get_itemId_embeddings
@@ -175,7 +237,16 @@ def main():
                     help='run the candidate-set leg instead: the masked entries beside the unmasked ones under a random mask of this fraction')
     ap.add_argument('--lists', type=int, default=None, metavar='C', choices=(0, 100, 1000, 4096),
                     help="run the per-user-list leg instead: a4r_topk_lists over C listed items per user beside the eager gather path (0: every C)")
+    ap.add_argument('--mmr', action='store_true',
+                    help='run the re-ranking leg instead: a4r_mmr_rerank beside the eager gather + bmm + K-round loop, pools of 100 and 256, E = 64 and 128')
     a = ap.parse_args()
+    if a.mmr:
+        for P in (100, 256):
+            for E in (64, 128):
+                name = f'mmr_p{P}_e{E}'
+                if not a.only or a.only == name:
+                    print(json.dumps(mmr_cfg(name, 32768, 65537, E, 10, P, 0.7, a.iters)), flush=True)
+        return
     if a.lists is not None:
         for C in ((100, 1000, 4096) if a.lists == 0 else (a.lists,)):
             for E in (64, 128):
