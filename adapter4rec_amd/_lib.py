@@ -5,6 +5,7 @@ raises -- there is no PyTorch / CPU fallback.  Tensors are passed as raw device 
 leading dimensions; kernels are enqueued on torch's current HIP stream.
 """
 import ctypes as C
+import importlib
 import math
 import os
 
@@ -193,13 +194,9 @@ def lib():
                 f'{LIB_PATH} not found: build it with `python -c "import __graft_entry__ as g; g.build()"` '
                 '(hipcc --offload-arch=gfx950).  adapter4rec_amd has no CPU / PyTorch fallback.')
         _lib = C.CDLL(LIB_PATH)
-        from ._lib_ce_bf16 import SCORE_CE_BF16_SIGNATURES            # (the bf16 cross-entropy head's exports: a table of their own, bottom of this file)
-        from ._lib_candidates import CANDIDATES_SIGNATURES            # (eval and top-K within a candidate set: likewise)
-        from ._lib_user_lists import USER_LISTS_SIGNATURES            # (top-K and rank within a list of each user's own: likewise)
-        from ._lib_eval_negatives import EVAL_NEGATIVES_SIGNATURES    # (the negatives of a sampled evaluation drawn on the device: likewise)
-        from ._lib_diversify import DIVERSIFY_SIGNATURES                # (the diversified re-ranking of a top-K list: likewise)
-        tables = dict(SIGNATURES, **SCORE_CE_BF16_SIGNATURES, **CANDIDATES_SIGNATURES, **USER_LISTS_SIGNATURES, **EVAL_NEGATIVES_SIGNATURES,
-                      **DIVERSIFY_SIGNATURES)
+        tables = dict(SIGNATURES)
+        for module, (table, _) in SATELLITES.items():                # (the satellites' exports: a table each, bottom of this file)
+            tables.update(getattr(importlib.import_module('.' + module, __package__), table))
         missing = [name for name in tables if not hasattr(_lib, name)]
         if missing:                   # a build from before an entry point was added (additions keep the ABI number: no argument list changes)
             _lib = None
@@ -941,43 +938,27 @@ def id_sample(seqs, rows, item_num, seed, draw, negatives, ids, log_mask, err):
                                _p(err)), 'a4r_id_sample')
 
 
-# The cross-entropy head on the bf16 MFMA (--ce_dtype bf16): declared in include/a4r_score_ce_bf16.h (which include/a4r.h includes) and bound in
-# _lib_ce_bf16.py with a signature table of its own, which lib() above checks and installs at load beside SIGNATURES.  Its wrappers and constants
-# are reachable under this module's name as well; they are resolved on first use, so either module can be imported first.
-_CE_BF16_NAMES = ('SCORE_CE_BF16_E', 'SCORE_CE_BF16_ROWS', 'SCORE_CE_BF16_SIGNATURES', 'cast_bf16', 'score_ce_bf16_bwd', 'score_ce_bf16_fwd',
-                  'score_ce_bf16_ranges', 'score_ce_bf16_ws_bytes')
-
-
-# Evaluation and top-K within a candidate set of items: include/a4r_candidates.h and _lib_candidates.py, held the same way.
-_CANDIDATES_NAMES = ('CANDIDATES_SIGNATURES', 'candidate_mask', 'eval_rank_cand', 'topk_items_cand')
-
-
-# Top-K and rank within a candidate list of each user's own: include/a4r_user_lists.h and _lib_user_lists.py, held the same way.
-_USER_LISTS_NAMES = ('USER_LISTS_SIGNATURES', 'LIST_MAX', 'topk_lists', 'eval_rank_lists')
-
-
-# The negatives of a sampled evaluation drawn on the device: include/a4r_eval_negatives.h and _lib_eval_negatives.py, held the same way.
-_EVAL_NEGATIVES_NAMES = ('EVAL_NEGATIVES_SIGNATURES', 'EVAL_NEG_SITE', 'EVAL_NEG_MAX', 'eval_draw_negatives', 'eval_rank_sampled')
-
-
-# The diversified re-ranking of a top-K list: include/a4r_diversify.h and _lib_diversify.py, held the same way.
-_DIVERSIFY_NAMES = ('DIVERSIFY_SIGNATURES', 'MMR_MAX_POOL', 'mmr_rerank')
+# Exports declared in a header of their own (which include/a4r.h includes) and bound in a satellite module with a signature table of its own, which
+# lib() above checks and installs at load beside SIGNATURES.  A satellite's table, wrappers and constants are reachable under this module's name as
+# well; they are resolved on first use, so either module can be imported first.  This is the one place a satellite is listed:
+#   module: (its signature table, the other names reachable here)
+SATELLITES = {
+    # the cross-entropy head on the bf16 MFMA (--ce_dtype bf16): include/a4r_score_ce_bf16.h
+    '_lib_ce_bf16': ('SCORE_CE_BF16_SIGNATURES', ('SCORE_CE_BF16_E', 'SCORE_CE_BF16_ROWS', 'cast_bf16', 'score_ce_bf16_bwd', 'score_ce_bf16_fwd',
+                                                  'score_ce_bf16_ranges', 'score_ce_bf16_ws_bytes')),
+    # evaluation and top-K within a candidate set of items: include/a4r_candidates.h
+    '_lib_candidates': ('CANDIDATES_SIGNATURES', ('candidate_mask', 'eval_rank_cand', 'topk_items_cand')),
+    # top-K and rank within a candidate list of each user's own: include/a4r_user_lists.h
+    '_lib_user_lists': ('USER_LISTS_SIGNATURES', ('LIST_MAX', 'topk_lists', 'eval_rank_lists')),
+    # the negatives of a sampled evaluation drawn on the device: include/a4r_eval_negatives.h
+    '_lib_eval_negatives': ('EVAL_NEGATIVES_SIGNATURES', ('EVAL_NEG_SITE', 'EVAL_NEG_MAX', 'eval_draw_negatives', 'eval_rank_sampled')),
+    # the diversified re-ranking of a top-K list: include/a4r_diversify.h
+    '_lib_diversify': ('DIVERSIFY_SIGNATURES', ('MMR_MAX_POOL', 'mmr_rerank')),
+}
 
 
 def __getattr__(name):
-    if name in _CE_BF16_NAMES:
-        from . import _lib_ce_bf16
-        return getattr(_lib_ce_bf16, name)
-    if name in _CANDIDATES_NAMES:
-        from . import _lib_candidates
-        return getattr(_lib_candidates, name)
-    if name in _USER_LISTS_NAMES:
-        from . import _lib_user_lists
-        return getattr(_lib_user_lists, name)
-    if name in _EVAL_NEGATIVES_NAMES:
-        from . import _lib_eval_negatives
-        return getattr(_lib_eval_negatives, name)
-    if name in _DIVERSIFY_NAMES:
-        from . import _lib_diversify
-        return getattr(_lib_diversify, name)
+    for module, (table, names) in SATELLITES.items():
+        if name == table or name in names:
+            return getattr(importlib.import_module('.' + module, __package__), name)
     raise AttributeError(f'module {__name__!r} has no attribute {name!r}')

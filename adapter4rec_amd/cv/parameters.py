@@ -2,6 +2,8 @@
 --local-rank)."""
 import argparse
 
+from ..data_utils.eval_flags import add_eval_flags
+
 
 def parse_args(argv=None):
     p = argparse.ArgumentParser()
@@ -39,17 +41,7 @@ def parse_args(argv=None):
                    help='--item_tower id: 1 draws the training batches on the GPU (data_utils.DeviceIdSampler, one a4r_id_sample launch per batch) '
                         'instead of BuildTrainDataset + DataLoader; same distribution, not the same draws')
     p.add_argument('--load_ckpt_name', type=str, default='None')
-    p.add_argument('--topk', type=int, default=10)                     # --mode recommend: items per user
-    p.add_argument('--recommend_out', type=str, default=None)          # --mode recommend: output file (default <model_dir>/recommend_<load_ckpt_name>.tsv)
-    p.add_argument('--candidate_items', type=str, default=None)        # --mode test / recommend: a file of item names, one per line -- rank and recommend among these items only
-    p.add_argument('--candidate_lists', type=str, default=None)        # --mode test / recommend: a file of `user_name \t item_name item_name ...` lines -- rank and recommend within each user's own list
-    p.add_argument('--diversify', type=str, default='none', choices=['none', 'mmr'])      # --mode recommend: mmr = re-rank each user's --mmr_pool best items by maximal marginal relevance, near-duplicates give way
-    p.add_argument('--mmr_lambda', type=float, default=0.7)            # the weight of relevance against similarity to the items already picked, in [0, 1]; 1 = the plain list
-    p.add_argument('--mmr_pool', type=int, default=100)                # how many of the best items the --topk picks are made from: --topk .. 256
-    p.add_argument('--eval_negatives', type=int, default=0)            # --mode test / the per-epoch evaluation: rank each target among N negatives drawn on the device (0 = off: the whole catalogue; at most 4096)
-    p.add_argument('--eval_neg_sampling', type=str, default='uniform', choices=['uniform', 'pop'])      # pop: in proportion to an item's occurrences in the training sequences
-    p.add_argument('--eval_neg_seed', type=int, default=20240607)      # the seed of the draws: the same negatives in every epoch, batch size and world size
-    p.add_argument('--eval_negatives_out', type=str, default=None)     # --mode test: write the test split's drawn negatives as a --candidate_lists file
+    add_eval_flags(p)                                                  # --topk .. --eval_negatives_out: shared with the text entry point
     p.add_argument('--label_screen', type=str, default='None')
     p.add_argument('--logging_num', type=int, default=8)
     p.add_argument('--testing_num', type=int, default=1)

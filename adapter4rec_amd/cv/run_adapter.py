@@ -23,9 +23,7 @@ from ..inject import freeze_all
 from ..optim import from_args as optimizer_from_args
 from . import Model, ModelCPC, ViTForImageClassification, ViTMAEModel
 from .data_utils import eval_model, get_itemId_embeddings, get_itemLMDB_embeddings, open_image_db, read_behaviors, read_images
-from ..data_utils.metrics import (check_eval_negatives_flag, eval_negatives_from_args, write_eval_negatives, candidate_lists_from_args, candidate_mask, candidates_from_args, check_candidate_flag, check_diversify_flag, diversify_from_args, read_candidate_lists, read_candidates,
-                                  write_recommendations)
-from ..data_utils.preprocess import read_behavior_names
+from ..data_utils.eval_flags import check_flags, eval_restriction, write_recommend_mode
 from .image_io import Build_Lmdb_Dataset, assemble_batch, collate_host
 from .inject import inject_adapters, optimizer_groups
 from .parameters import parse_args
@@ -101,19 +99,15 @@ def build_model(args, item_num, use_modal, cv_model, local_rank, Log_file, model
     return model.to(local_rank), start_epoch, ckpt2
 
 
-def run_eval_once(model, db, item_id_to_keys, user_history, users_eval, batch_size, item_num, mode, local_rank, args, Log_file, candidates=None, candidate_lists=None, eval_negatives=None):
+def run_eval_once(model, db, item_id_to_keys, user_history, users_eval, batch_size, item_num, mode, local_rank, args, Log_file, **restriction):
+    """``restriction``: eval_model's candidates / candidate_lists / eval_negatives, as eval_flags.eval_restriction gives them"""
     t0 = time.time()
     Log_file.info('Validating...')
     if db is None:                                                     # --item_tower id: the table itself (run_adapter.py:275-279)
         emb = get_itemId_embeddings(model, item_num, batch_size, args, local_rank)
     else:
         emb = get_itemLMDB_embeddings(model, item_num, item_id_to_keys, batch_size, args, local_rank, db=db)
-    kw = {} if candidates is None else dict(candidates=candidates)      # --candidate_items: ranked among, and averaged over targets within, the candidate set
-    if candidate_lists is not None:                                     # --candidate_lists: ranked within the user's own list, averaged over the users who have one
-        kw = dict(candidate_lists=candidate_lists)
-    if eval_negatives is not None:                                      # --eval_negatives: ranked among negatives drawn on the device, averaged over the users who have a candidate
-        kw = dict(eval_negatives=eval_negatives)
-    hit10 = eval_model(model, user_history, users_eval, emb, batch_size, args, item_num, Log_file, mode, local_rank, **kw)
+    hit10 = eval_model(model, user_history, users_eval, emb, batch_size, args, item_num, Log_file, mode, local_rank, **restriction)
     report_time_eval(t0, Log_file)
     return hit10
 
@@ -175,8 +169,9 @@ def train(args, use_modal, local_rank, Log_file, Log_screen, model_dir, start_ti
         train_dl = DataLoader(train_dataset, batch_size=args.batch_size, num_workers=0, sampler=sampler, collate_fn=_collate)
     model, start_epoch, ckpt2 = build_model(args, item_num, use_modal, cv_model, local_rank, Log_file, model_dir)
     model = FlatDDP(model, device_ids=[local_rank], output_device=local_rank)
-    neg = eval_negatives_from_args(args, users_train, item_num, Log_file)
-    ekw = {} if neg is None else dict(eval_negatives=neg)             # --eval_negatives; without the flag the calls are the ones made before
+    # --eval_negatives (the only restriction training takes); without the flag the calls are the ones made before
+    ekw = eval_restriction(args, os.path.join(args.root_data_dir, args.dataset, args.behaviors), before_name2id, users_train, hist_test, users_test,
+                           item_num, next(model.parameters()).device, Log_file)
     optimizer = optimizer_from_args(optimizer_groups(model, args), args)      # --optimizer / --weight_decay / --max_grad_norm; default: FusedAdam
     if ckpt2 is not None:
         optimizer.load_state_dict(ckpt2['optimizer'])
@@ -246,21 +241,8 @@ def test(args, use_modal, local_rank, Log_file, Log_screen, model_dir, start_tim
     db = open_image_db(os.path.join(args.root_data_dir, args.dataset, args.lmdb_data)) if use_modal else None
     model, _, _ = build_model(args, item_num, use_modal, cv_model, local_rank, Log_file, model_dir)
     model = FlatDDP(model, device_ids=[local_rank], output_device=local_rank)
-    cand = candidates_from_args(args, os.path.join(args.root_data_dir, args.dataset, args.behaviors), before_name2id, Log_file)
-    # --candidate_items: the mask is uploaded once, for both splits; without the flag the calls are the ones made before
-    kw = {} if cand is None else dict(candidates=candidate_mask(cand, item_num + 1, next(model.parameters()).device))
-    lists = candidate_lists_from_args(args, os.path.join(args.root_data_dir, args.dataset, args.behaviors), before_name2id, Log_file)
-    if lists is not None:                                              # --candidate_lists (never beside --candidate_items: main refuses the pair)
-        kw = dict(candidate_lists=lists)
-    neg = eval_negatives_from_args(args, users_train, item_num, Log_file)
-    if neg is not None:                                                # --eval_negatives (never beside either candidate flag: main refuses the pair)
-        kw = dict(eval_negatives=neg)
-        if args.eval_negatives_out and dist.get_rank() == 0:
-            user_names, item_names = read_behavior_names(os.path.join(args.root_data_dir, args.dataset, args.behaviors), before_name2id,
-                                                         args.max_seq_len, args.min_seq_len)
-            k = write_eval_negatives(neg, hist_test, users_test, item_num + 1, args, user_names, item_names, args.eval_negatives_out,
-                                     next(model.parameters()).device)
-            Log_file.info(f'eval negatives: the draws of the test split for {k} users -> {args.eval_negatives_out}')
+    kw = eval_restriction(args, os.path.join(args.root_data_dir, args.dataset, args.behaviors), before_name2id, users_train, hist_test, users_test,
+                          item_num, next(model.parameters()).device, Log_file)
     run_eval_once(model, db, item_id_to_keys, hist_valid, users_valid, 256, item_num, 'valid', local_rank, args, Log_file, **kw)
     run_eval_once(model, db, item_id_to_keys, hist_test, users_test, 256, item_num, 'test', local_rank, args, Log_file, **kw)
 
@@ -274,7 +256,6 @@ def recommend(args, use_modal, local_rank, Log_file, Log_screen, model_dir, star
     path = os.path.join(args.root_data_dir, args.dataset, args.behaviors)
     before_keys, before_name2id = read_images(os.path.join(args.root_data_dir, args.dataset, args.images))
     item_num, item_id_to_keys, _, _, users_test, _, hist_test = read_behaviors(path, before_keys, before_name2id, args.max_seq_len, args.min_seq_len, Log_file)
-    user_names, item_names = read_behavior_names(path, before_name2id, args.max_seq_len, args.min_seq_len)
     db = open_image_db(os.path.join(args.root_data_dir, args.dataset, args.lmdb_data)) if use_modal else None
     model, _, _ = build_model(args, item_num, use_modal, cv_model, local_rank, Log_file, model_dir)
     model = FlatDDP(model, device_ids=[local_rank], output_device=local_rank)
@@ -282,20 +263,12 @@ def recommend(args, use_modal, local_rank, Log_file, Log_screen, model_dir, star
         emb = get_itemId_embeddings(model, item_num, 256, args, local_rank)
     else:
         emb = get_itemLMDB_embeddings(model, item_num, item_id_to_keys, 256, args, local_rank, db=db)
-    out = args.recommend_out or os.path.join(model_dir, f'recommend_{args.load_ckpt_name}.tsv')
-    out = write_recommendations(model, users_test, hist_test, emb, args.topk, 256, args, user_names, item_names, out,
-                                candidates=read_candidates(args.candidate_items, item_names) if args.candidate_items else None,
-                                candidate_lists=read_candidate_lists(args.candidate_lists, user_names, item_names) if args.candidate_lists else None,
-                                diversify=diversify_from_args(args, Log_file), Log_file=Log_file)
-    if out:
-        Log_file.info(f'recommend: top-{args.topk} lists of {len(users_test)} users -> {out}')
+    write_recommend_mode(args, model, users_test, hist_test, emb, 256, path, before_name2id, model_dir, Log_file)
 
 
 def main(argv=None):
     args = parse_args(argv)
-    check_candidate_flag(args)
-    check_eval_negatives_flag(args)
-    check_diversify_flag(args)
+    check_flags(args)
     local_rank = args.local_rank if args.local_rank >= 0 else int(os.environ.get('LOCAL_RANK', 0))
     torch.cuda.set_device(local_rank)
     dist.init_process_group(backend='nccl', init_method='env://')      # 'nccl' is RCCL on ROCm

@@ -1,0 +1,151 @@
+"""The flags that restrict or re-rank what evaluation and recommendation range over (--topk .. --eval_negatives_out), for both entry points
+(run.py, cv/run_adapter.py): their declaration, their refusals, and their translation into the arguments of data_utils.metrics (eval_model's
+restriction, write_recommendations' call).  No kernel is called from here."""
+import math
+import os
+
+import torch.distributed as dist
+
+from .._lib_diversify import MMR_MAX_POOL
+from .._lib_user_lists import LIST_MAX
+from .metrics import (Diversify, EvalNegatives, candidate_mask, item_counts, read_candidate_lists, read_candidates, write_eval_negatives,
+                      write_recommendations)
+from .preprocess import read_behavior_names
+
+
+def add_eval_flags(p):
+    p.add_argument('--topk', type=int, default=10)                     # --mode recommend: items per user
+    p.add_argument('--recommend_out', type=str, default=None)          # --mode recommend: output file (default <model_dir>/recommend_<load_ckpt_name>.tsv)
+    p.add_argument('--candidate_items', type=str, default=None)        # --mode test / recommend: a file of item names, one per line -- rank and recommend among these items only
+    p.add_argument('--candidate_lists', type=str, default=None)        # --mode test / recommend: a file of `user_name \t item_name item_name ...` lines -- rank and recommend within each user's own list
+    p.add_argument('--diversify', type=str, default='none', choices=['none', 'mmr'])      # --mode recommend: mmr = re-rank each user's --mmr_pool best items by maximal marginal relevance, near-duplicates give way
+    p.add_argument('--mmr_lambda', type=float, default=0.7)            # the weight of relevance against similarity to the items already picked, in [0, 1]; 1 = the plain list
+    p.add_argument('--mmr_pool', type=int, default=100)                # how many of the best items the --topk picks are made from: --topk .. 256
+    p.add_argument('--eval_negatives', type=int, default=0)            # --mode test / the per-epoch evaluation: rank each target among N negatives drawn on the device (0 = off: the whole catalogue; at most 4096)
+    p.add_argument('--eval_neg_sampling', type=str, default='uniform', choices=['uniform', 'pop'])      # pop: in proportion to an item's occurrences in the training sequences
+    p.add_argument('--eval_neg_seed', type=int, default=20240607)      # the seed of the draws: the same negatives in every epoch, batch size and world size
+    p.add_argument('--eval_negatives_out', type=str, default=None)     # --mode test: write the test split's drawn negatives as a --candidate_lists file
+
+
+def check_flags(args):
+    """Both entry points' refusals, before anything is set up (no device, no process group)."""
+    check_candidate_flag(args)
+    check_eval_negatives_flag(args)
+    check_diversify_flag(args)
+
+
+def check_candidate_flag(args):
+    """--candidate_items and --candidate_lists restrict --mode test and --mode recommend; training and its per-epoch evaluation are not
+    restricted by them, so any other mode refuses either flag instead of ignoring it.  The two together are refused as well: a user's own list
+    is the restriction, not one more beside a shared set."""
+    for flag in ('candidate_items', 'candidate_lists'):
+        if getattr(args, flag, None) and not ('test' in args.mode or args.mode == 'recommend'):
+            raise ValueError(f'--{flag} is honoured by --mode test and --mode recommend only, not by --mode {args.mode} '
+                             '(training and its per-epoch evaluation range over the whole catalogue)')
+    if getattr(args, 'candidate_items', None) and getattr(args, 'candidate_lists', None):
+        raise ValueError('--candidate_lists (a list per user) and --candidate_items (one set for all users) cannot be combined: give one of them')
+
+
+def check_eval_negatives_flag(args):
+    """--eval_negatives N (with --eval_neg_sampling / --eval_neg_seed) is honoured by --mode test and by the per-epoch evaluation of training;
+    it is refused under --mode recommend and beside --candidate_items / --candidate_lists (a user's drawn negatives are the restriction), and
+    --eval_negatives_out is --mode test's."""
+    n = int(getattr(args, 'eval_negatives', 0) or 0)
+    out = getattr(args, 'eval_negatives_out', None)
+    if n == 0:
+        if out:
+            raise ValueError('--eval_negatives_out needs --eval_negatives N')
+        return
+    if not 1 <= n <= LIST_MAX:
+        raise ValueError(f'--eval_negatives {n}: outside 1 .. {LIST_MAX}')
+    if args.mode == 'recommend':
+        raise ValueError('--eval_negatives is an evaluation protocol: it is not honoured by --mode recommend')
+    for flag in ('candidate_items', 'candidate_lists'):
+        if getattr(args, flag, None):
+            raise ValueError(f'--eval_negatives and --{flag} cannot be combined: the drawn negatives are the candidates '
+                             '(to replay a draw, write it with --eval_negatives_out and give the file to --candidate_lists alone)')
+    if out and 'test' not in args.mode:
+        raise ValueError(f'--eval_negatives_out is honoured by --mode test only, not by --mode {args.mode}')
+    if not 0 <= int(args.eval_neg_seed) < 2 ** 64:
+        raise ValueError(f'--eval_neg_seed {args.eval_neg_seed}: outside 0 .. 2^64 - 1')
+
+
+def check_diversify_flag(args):
+    """--diversify mmr (with --mmr_lambda / --mmr_pool) re-ranks the lists of --mode recommend; every other mode refuses it instead of ignoring
+    it.  The pool is a top-K output that the --topk list is cut from: topk <= pool <= 256."""
+    if getattr(args, 'diversify', 'none') == 'none':
+        return
+    if args.mode != 'recommend':
+        raise ValueError(f'--diversify {args.diversify} is honoured by --mode recommend only, not by --mode {args.mode}')
+    lam = float(args.mmr_lambda)
+    if math.isnan(lam) or not 0.0 <= lam <= 1.0:
+        raise ValueError(f'--mmr_lambda {args.mmr_lambda}: outside [0, 1]')
+    if not int(args.topk) <= int(args.mmr_pool) <= MMR_MAX_POOL:
+        raise ValueError(f'--mmr_pool {args.mmr_pool}: outside --topk = {args.topk} .. {MMR_MAX_POOL}')
+
+
+def _candidates_from_args(args, user_names, item_names, Log_file):
+    """--candidate_items FILE / --candidate_lists FILE -> (bool array [item_num + 1] or None, {uid: [item ids]} or None) in the numbering
+    read_behaviors gives users and items (``user_names``, ``item_names``: preprocess.read_behavior_names)."""
+    mask = lists = None
+    if getattr(args, 'candidate_items', None):
+        mask = read_candidates(args.candidate_items, item_names)
+        Log_file.info(f'candidate items: {int(mask.sum())} of {len(item_names) - 1} from {args.candidate_items}')
+    if getattr(args, 'candidate_lists', None):
+        lists = read_candidate_lists(args.candidate_lists, user_names, item_names)
+        Log_file.info(f'candidate lists: {len(lists)} of {len(user_names)} users, {sum(len(v) for v in lists.values())} items in all, from {args.candidate_lists}')
+    return mask, lists
+
+
+def eval_negatives_from_args(args, users_train, item_num, Log_file):
+    """--eval_negatives N -> an EvalNegatives, or None without the flag (then nothing changes)."""
+    n = int(getattr(args, 'eval_negatives', 0) or 0)
+    if n == 0:
+        return None
+    pop = args.eval_neg_sampling == 'pop'
+    spec = EvalNegatives(n, seed=args.eval_neg_seed, counts=item_counts(users_train, item_num) if pop else None)
+    Log_file.info(f'eval negatives: {n} per user, {args.eval_neg_sampling} sampling, seed {spec.seed}'
+                  + (f', {int((spec.counts > 0).sum())} of {item_num} items with a training occurrence' if pop else ''))
+    return spec
+
+
+def eval_restriction(args, behaviors_path, name2id, users_train, hist_test, users_test, item_num, dev, Log_file):
+    """The flags as eval_model's restriction keywords, for every evaluation of a run: {} without a flag (the calls are then the ones made
+    before), else one of ``candidates`` (--candidate_items: the mask uploaded to ``dev`` here, once for both splits), ``candidate_lists``
+    (--candidate_lists) and ``eval_negatives`` (--eval_negatives; with --eval_negatives_out, rank 0 writes the test split's draws).  check_flags
+    has refused every pair of them, and the candidate flags outside --mode test.  The behaviours file is read for its names at most once."""
+    out = getattr(args, 'eval_negatives_out', None) and dist.get_rank() == 0
+    user_names = item_names = None
+    if getattr(args, 'candidate_items', None) or getattr(args, 'candidate_lists', None) or out:
+        user_names, item_names = read_behavior_names(behaviors_path, name2id, args.max_seq_len, args.min_seq_len)
+    mask, lists = _candidates_from_args(args, user_names, item_names, Log_file)
+    kw = {} if mask is None else dict(candidates=candidate_mask(mask, item_num + 1, dev))
+    if lists is not None:
+        kw = dict(candidate_lists=lists)
+    neg = eval_negatives_from_args(args, users_train, item_num, Log_file)
+    if neg is not None:
+        kw = dict(eval_negatives=neg)
+        if out:
+            k = write_eval_negatives(neg, hist_test, users_test, item_num + 1, args, user_names, item_names, args.eval_negatives_out, dev)
+            Log_file.info(f'eval negatives: the draws of the test split for {k} users -> {args.eval_negatives_out}')
+    return kw
+
+
+def recommend_out_path(args, model_dir):
+    return args.recommend_out or os.path.join(model_dir, f'recommend_{args.load_ckpt_name}.tsv')
+
+
+def write_recommend_mode(args, model, users_test, hist_test, item_embeddings, batch_size, behaviors_path, name2id, model_dir, Log_file):
+    """The tail of --mode recommend in both entry points: the --topk next items after every user's whole known sequence of the test split, within
+    --candidate_items / --candidate_lists and re-ranked under --diversify mmr, written by rank 0 to --recommend_out under the names of the
+    behaviours file."""
+    user_names, item_names = read_behavior_names(behaviors_path, name2id, args.max_seq_len, args.min_seq_len)
+    mask, lists = _candidates_from_args(args, user_names, item_names, Log_file)
+    spec = None
+    if getattr(args, 'diversify', 'none') != 'none':
+        spec = Diversify(args.mmr_lambda, args.mmr_pool)
+        Log_file.info(f'diversify: mmr, lambda {spec.lam:g}, pool {spec.pool}')
+    out = write_recommendations(model, users_test, hist_test, item_embeddings, args.topk, batch_size, args, user_names, item_names,
+                                recommend_out_path(args, model_dir), candidates=mask, candidate_lists=lists, diversify=spec, Log_file=Log_file)
+    if out:
+        Log_file.info(f'recommend: top-{args.topk} lists of {len(users_test)} users -> {out}')

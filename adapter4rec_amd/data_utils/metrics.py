@@ -56,8 +56,7 @@ def enc_dim(model, args):
 def _my_shard(n):
     """The item sweep is sharded over the data-parallel ranks (the reference encodes all N + 1 items on EVERY rank,
     metrics.py:62-79): rank r takes rows [r * chunk, (r + 1) * chunk) and the table is all-gathered."""
-    world = dist.get_world_size() if dist.is_initialized() else 1
-    r = dist.get_rank() if dist.is_initialized() else 0
+    world, r = _world_rank()
     chunk = (n + world - 1) // world
     return min(r * chunk, n), min((r + 1) * chunk, n), chunk, world
 
@@ -67,9 +66,51 @@ def _gather_shards(mine, n, chunk, world):
         return mine
     pad = torch.zeros(chunk, mine.shape[1], dtype=mine.dtype, device=mine.device)
     pad[:mine.shape[0]] = mine
-    parts = [torch.zeros_like(pad) for _ in range(world)]
-    dist.all_gather(parts, pad)
-    return torch.cat(parts, 0)[:n].contiguous()
+    return _gather_cat(pad, world)[:n].contiguous()
+
+
+def _world_rank():
+    return (dist.get_world_size(), dist.get_rank()) if dist.is_initialized() else (1, 0)
+
+
+def _shard_users(n_users, batch_size):
+    """-> (world, rank, this rank's user ids): the run of consecutive users SequentialDistributedSampler hands the rank at this batch size, its
+    tail repeating the last users.  eval_model and write_recommendations shard their users the same way."""
+    world, rank = _world_rank()
+    return world, rank, SequentialDistributedSampler(range(n_users), batch_size, rank=rank, num_replicas=world).indices()
+
+
+def _gather_cat(t, world):
+    """The ranks' equal-shaped tensors concatenated along dim 0 in rank order; ``t`` itself in a single process."""
+    if world == 1:
+        return t
+    parts = [torch.zeros_like(t) for _ in range(world)]
+    dist.all_gather(parts, t)
+    return torch.cat(parts)
+
+
+def _left_pad(flat, lens, width):
+    """Rows of ``lens[i]`` item ids each, flattened in row order -> ids int64 / mask fp32 [n, width]: every row right-aligned, pad = width - len on
+    the left (BuildEvalDataset.__getitem__'s layout), the mask 1 on the real positions."""
+    n = lens.size
+    rows = np.repeat(np.arange(n), lens)
+    cols = (np.arange(int(lens.sum())) - np.repeat(np.cumsum(lens) - lens, lens)) + np.repeat(width - lens, lens)
+    ids = np.zeros((n, width), dtype=np.int64)
+    mask = np.zeros((n, width), dtype=np.float32)
+    ids[rows, cols] = flat
+    mask[rows, cols] = 1.0
+    return ids, mask
+
+
+def _csr_int32(rows):
+    """A list of int64 id arrays as the kernels read per-user lists: (ptr int64 [n + 1], flat int32 ids + one spare 0, lens int64 [n])."""
+    lens = np.fromiter((x.size for x in rows), dtype=np.int64, count=len(rows))
+    ptr = np.zeros(len(rows) + 1, dtype=np.int64)
+    np.cumsum(lens, out=ptr[1:])
+    flat = np.concatenate(rows + [np.zeros(1, np.int64)])
+    # ids outside int32 can never name a table row; clamp them to -1 (ignored like any id outside 1 .. N1-1) instead of letting them wrap
+    flat = np.where((flat < 0) | (flat > np.iinfo(np.int32).max), -1, flat).astype(np.int32)
+    return ptr, flat, lens
 
 
 _PREP = {}        # (id(eval_seq), id(user_history), users, tokens, Lm, device) -> the evaluation set as device tensors (built once, reused every epoch)
@@ -92,17 +133,10 @@ def _prepare_eval_set(eval_seq, user_history, Lm, dev):
         raise ValueError(f'an evaluation sequence of {int(lens.max())} items exceeds max_seq_len + 1 = {Lm}')
     flat = np.fromiter(itertools.chain.from_iterable(eval_seq[u] for u in range(n)), dtype=np.int64, count=total)
     ends = np.cumsum(lens)
-    starts = ends - lens
     target = flat[ends - 1] if n else np.zeros(0, np.int64)
     keep = np.ones(total, dtype=bool)
     keep[ends - 1] = False                                    # every sequence's last item is the target, the rest its inputs
-    rows = np.repeat(np.arange(n), lens - 1)
-    within = np.arange(total)[keep] - np.repeat(starts, lens - 1)
-    cols = np.repeat(Lm - lens, lens - 1) + within            # left padding: pad = Lm - len(seq)
-    ids = np.zeros((n, Lm - 1), dtype=np.int64)
-    mask = np.zeros((n, Lm - 1), dtype=np.float32)
-    ids[rows, cols] = flat[keep]
-    mask[rows, cols] = 1.0
+    ids, mask = _left_pad(flat[keep], lens - 1, Lm - 1)       # left padding: pad = Lm - len(seq)
     hv = [user_history[u] for u in range(n)]
     if n and isinstance(hv[0], torch.Tensor):                 # preprocess.py:58-59: one LongTensor per user
         hl = np.fromiter((t.shape[0] if t.dim() == 1 else t.numel() for t in hv), dtype=np.int64, count=n)
@@ -123,6 +157,15 @@ def _prepare_eval_set(eval_seq, user_history, Lm, dev):
         _PREP.clear()
     _PREP[key] = prep
     return prep
+
+
+def _batch_slices(P, a, b):
+    """The consecutive users a .. b - 1 of a prepared evaluation set as the kernels read them: (history ptr int32 [b - a + 1], counted from the
+    batch's first id; the history ids; the targets int32 [b - a]) -- slices of the prepared tensors, no gather, no host-device round trip for
+    the history count."""
+    h0, h1 = int(P['hptr_host'][a]), int(P['hptr_host'][b])
+    # (+ 1: the kernel's table is never empty; the store ends in one spare 0)
+    return (P['hptr'][a:b + 1] - h0).to(torch.int32), P['hflat32'][h0:h1 + 1], P['target32'][a:b]
 
 
 def candidate_mask(candidates, n1, dev):
@@ -169,18 +212,6 @@ def read_candidates(path, item_names):
     return mask
 
 
-def check_candidate_flag(args):
-    """--candidate_items and --candidate_lists restrict --mode test and --mode recommend; training and its per-epoch evaluation are not
-    restricted by them, so any other mode refuses either flag instead of ignoring it.  The two together are refused as well: a user's own list
-    is the restriction, not one more beside a shared set."""
-    for flag in ('candidate_items', 'candidate_lists'):
-        if getattr(args, flag, None) and not ('test' in args.mode or args.mode == 'recommend'):
-            raise ValueError(f'--{flag} is honoured by --mode test and --mode recommend only, not by --mode {args.mode} '
-                             '(training and its per-epoch evaluation range over the whole catalogue)')
-    if getattr(args, 'candidate_items', None) and getattr(args, 'candidate_lists', None):
-        raise ValueError('--candidate_lists (a list per user) and --candidate_items (one set for all users) cannot be combined: give one of them')
-
-
 class Diversify:
     """recommend's ``diversify``: re-rank each user's ``pool`` best items by maximal marginal relevance (a4r_mmr_rerank; the rule is in
     include/a4r_diversify.h) -- k greedy picks by ``lam`` * relevance - (1 - ``lam``) * (largest cosine to an item already picked), relevance the
@@ -193,41 +224,6 @@ class Diversify:
             raise ValueError(f'diversify: lambda = {self.lam} outside [0, 1]')
         if not 1 <= self.pool <= MMR_MAX_POOL:
             raise ValueError(f'diversify: pool = {self.pool} outside 1 .. {MMR_MAX_POOL}')
-
-
-def check_diversify_flag(args):
-    """--diversify mmr (with --mmr_lambda / --mmr_pool) re-ranks the lists of --mode recommend; every other mode refuses it instead of ignoring
-    it.  The pool is a top-K output that the --topk list is cut from: topk <= pool <= 256."""
-    if getattr(args, 'diversify', 'none') == 'none':
-        return
-    if args.mode != 'recommend':
-        raise ValueError(f'--diversify {args.diversify} is honoured by --mode recommend only, not by --mode {args.mode}')
-    lam = float(args.mmr_lambda)
-    if math.isnan(lam) or not 0.0 <= lam <= 1.0:
-        raise ValueError(f'--mmr_lambda {args.mmr_lambda}: outside [0, 1]')
-    if not int(args.topk) <= int(args.mmr_pool) <= MMR_MAX_POOL:
-        raise ValueError(f'--mmr_pool {args.mmr_pool}: outside --topk = {args.topk} .. {MMR_MAX_POOL}')
-
-
-def diversify_from_args(args, Log_file):
-    """The runners' --diversify mmr -> a Diversify, or None without the flag (then nothing changes)."""
-    if getattr(args, 'diversify', 'none') == 'none':
-        return None
-    spec = Diversify(args.mmr_lambda, args.mmr_pool)
-    Log_file.info(f'diversify: mmr, lambda {spec.lam:g}, pool {spec.pool}')
-    return spec
-
-
-def candidates_from_args(args, behaviors_path, name2id, Log_file):
-    """The runners' --candidate_items FILE -> bool array [item_num + 1] in the numbering read_behaviors gives the items, or None without the
-    flag."""
-    if not getattr(args, 'candidate_items', None):
-        return None
-    from .preprocess import read_behavior_names
-    _, item_names = read_behavior_names(behaviors_path, name2id, args.max_seq_len, args.min_seq_len)
-    mask = read_candidates(args.candidate_items, item_names)
-    Log_file.info(f'candidate items: {int(mask.sum())} of {len(item_names) - 1} from {args.candidate_items}')
-    return mask
 
 
 def _user_list(candidate_lists, u):
@@ -254,12 +250,7 @@ def candidate_lists_csr(candidate_lists, uids):
             raise ValueError(f'user {int(u)}: candidate list of {x.size} items exceeds A4R_LIST_MAX = {LIST_MAX} (never truncated); '
                              'a catalogue-scale set belongs in a shared candidate set (--candidate_items)')
         ls.append(x)
-    lens = np.fromiter((x.size for x in ls), dtype=np.int64, count=len(ls))
-    ptr = np.zeros(len(ls) + 1, dtype=np.int64)
-    np.cumsum(lens, out=ptr[1:])
-    flat = np.concatenate(ls + [np.zeros(1, np.int64)])
-    flat = np.where((flat < 0) | (flat > np.iinfo(np.int32).max), -1, flat).astype(np.int32)
-    return ptr, flat, lens
+    return _csr_int32(ls)
 
 
 def _both_refused(candidates, candidate_lists, eval_negatives=None):
@@ -299,17 +290,6 @@ def read_candidate_lists(path, user_names, item_names):
         if bad:
             raise ValueError(f'{path}: {len(bad)} name(s) that are no {what} of this dataset: ' + ', '.join(bad[:5]) + (' ...' if len(bad) > 5 else ''))
     return out
-
-
-def candidate_lists_from_args(args, behaviors_path, name2id, Log_file):
-    """The runners' --candidate_lists FILE -> {uid: [item ids]} in the numbering read_behaviors gives users and items, or None without the flag."""
-    if not getattr(args, 'candidate_lists', None):
-        return None
-    from .preprocess import read_behavior_names
-    user_names, item_names = read_behavior_names(behaviors_path, name2id, args.max_seq_len, args.min_seq_len)
-    lists = read_candidate_lists(args.candidate_lists, user_names, item_names)
-    Log_file.info(f'candidate lists: {len(lists)} of {len(user_names)} users, {sum(len(v) for v in lists.values())} items in all, from {args.candidate_lists}')
-    return lists
 
 
 EVAL_NEG_SEED = 20240607          # --eval_neg_seed's default: one constant for every rank, epoch and run (a draw is keyed by the GLOBAL user id)
@@ -362,42 +342,6 @@ def item_counts(users_train, item_num):
     return np.bincount(flat[(flat > 0) & (flat <= item_num)], minlength=item_num + 1).astype(np.int64)
 
 
-def check_eval_negatives_flag(args):
-    """--eval_negatives N (with --eval_neg_sampling / --eval_neg_seed) is honoured by --mode test and by the per-epoch evaluation of training;
-    it is refused under --mode recommend and beside --candidate_items / --candidate_lists (a user's drawn negatives are the restriction), and
-    --eval_negatives_out is --mode test's."""
-    n = int(getattr(args, 'eval_negatives', 0) or 0)
-    out = getattr(args, 'eval_negatives_out', None)
-    if n == 0:
-        if out:
-            raise ValueError('--eval_negatives_out needs --eval_negatives N')
-        return
-    if not 1 <= n <= LIST_MAX:
-        raise ValueError(f'--eval_negatives {n}: outside 1 .. {LIST_MAX}')
-    if args.mode == 'recommend':
-        raise ValueError('--eval_negatives is an evaluation protocol: it is not honoured by --mode recommend')
-    for flag in ('candidate_items', 'candidate_lists'):
-        if getattr(args, flag, None):
-            raise ValueError(f'--eval_negatives and --{flag} cannot be combined: the drawn negatives are the candidates '
-                             '(to replay a draw, write it with --eval_negatives_out and give the file to --candidate_lists alone)')
-    if out and 'test' not in args.mode:
-        raise ValueError(f'--eval_negatives_out is honoured by --mode test only, not by --mode {args.mode}')
-    if not 0 <= int(args.eval_neg_seed) < 2 ** 64:
-        raise ValueError(f'--eval_neg_seed {args.eval_neg_seed}: outside 0 .. 2^64 - 1')
-
-
-def eval_negatives_from_args(args, users_train, item_num, Log_file):
-    """The runners' --eval_negatives N -> an EvalNegatives, or None without the flag (then nothing changes)."""
-    n = int(getattr(args, 'eval_negatives', 0) or 0)
-    if n == 0:
-        return None
-    pop = args.eval_neg_sampling == 'pop'
-    spec = EvalNegatives(n, seed=args.eval_neg_seed, counts=item_counts(users_train, item_num) if pop else None)
-    Log_file.info(f'eval negatives: {n} per user, {args.eval_neg_sampling} sampling, seed {spec.seed}'
-                  + (f', {int((spec.counts > 0).sum())} of {item_num} items with a training occurrence' if pop else ''))
-    return spec
-
-
 def _negatives_valid(spec, P, uid, n1, dev):
     """float [len(uid)]: 1 where the user has an item left to draw (m >= 1 in the draw rule).  Only a catalogue that a history can exhaust
     (uniform: at most 265 items; weighted: all but the 265 heaviest items weigh nothing) is looked at user by user, on the device."""
@@ -428,15 +372,13 @@ def write_eval_negatives(spec, user_history, eval_seq, n1, args, user_names, ite
     n_users = len(eval_seq)
     step = int(os.environ.get('A4R_EVAL_USER_BATCH', 0)) or 8192
     err = torch.zeros(1, dtype=torch.int32, device=dev)
-    hptr_host = P['hptr_host']
     written = 0
     with open(path, 'w') as f:
         for a in range(0, n_users, step):
             b = min(a + step, n_users)
-            h0, h1 = int(hptr_host[a]), int(hptr_host[b])
             out = torch.zeros(b - a, spec.n, dtype=torch.int32, device=dev)
-            L.eval_draw_negatives((P['hptr'][a:b + 1] - h0).to(torch.int32), P['hflat32'][h0:h1 + 1], P['target32'][a:b],
-                                  torch.arange(a, b, dtype=torch.int32, device=dev), cdf, spec.seed, n1, out, err)
+            ptr, hist, target = _batch_slices(P, a, b)
+            L.eval_draw_negatives(ptr, hist, target, torch.arange(a, b, dtype=torch.int32, device=dev), cdf, spec.seed, n1, out, err)
             ids = out.cpu().numpy()
             for u in range(a, b):
                 if ids[u - a, 0] != 0:                             # (no candidate: all zeros, no line -- the user is left out of the means either way)
@@ -478,13 +420,12 @@ def eval_ranks(model, user_history, eval_seq, item_embeddings, test_batch_size, 
         neg_cdf, _, _ = eval_negatives.weights(emb.shape[0], dev)
         neg_err = torch.zeros(1, dtype=torch.int32, device=dev)
     # SequentialDistributedSampler hands every rank a run of consecutive users (its tail repeats the last ones): a batch of CONSECUTIVE users is a
-    # slice of every prepared tensor -- no gather, no host-device round trip for the history count
+    # slice of every prepared tensor (_batch_slices)
     runs = np.flatnonzero(np.diff(uid_np) != 1) + 1
     bounds = np.concatenate([[0], runs, [uid_np.size]])
     # the reference's test_batch_size (256 - 512 users) is sized for ITS [users, items] score matrix; nothing of that size exists here: the user tower
     # and the rank kernel take 8 192 users per call (A4R_EVAL_USER_BATCH overrides it)
     step = int(os.environ.get('A4R_EVAL_USER_BATCH', 0)) or max(int(test_batch_size), 8192)
-    hptr_host = P['hptr_host']
     ranks = []
     with torch.no_grad():
         for r0, r1 in zip(bounds[:-1], bounds[1:]):
@@ -494,21 +435,19 @@ def eval_ranks(model, user_history, eval_seq, item_embeddings, test_batch_size, 
                 b = a + nb
                 input_embs = emb[P['ids'][a:b].reshape(-1)].view(nb, Lm - 1, E)
                 prec = inner.user_encoder(input_embs, P['mask'][a:b], None)[:, -1].contiguous()
-                h0, h1 = int(hptr_host[a]), int(hptr_host[b])
-                ptr = (P['hptr'][a:b + 1] - h0).to(torch.int32)
-                hist = P['hflat32'][h0:h1 + 1]                 # (+ 1: the kernel's table is never empty; the store ends in one spare 0)
+                ptr, hist, target = _batch_slices(P, a, b)
                 rank = torch.zeros(nb, dtype=torch.int32, device=dev)
                 if eval_negatives is not None:
-                    L.eval_rank_sampled(prec, emb, P['target32'][a:b], ptr, hist, torch.arange(a, b, dtype=torch.int32, device=dev), neg_cdf,
+                    L.eval_rank_sampled(prec, emb, target, ptr, hist, torch.arange(a, b, dtype=torch.int32, device=dev), neg_cdf,
                                         eval_negatives.seed, eval_negatives.n, rank, neg_err)
                 elif candidate_lists is not None:
                     l0, l1 = int(lptr[s0]), int(lptr[s0 + nb])
-                    L.eval_rank_lists(prec, emb, P['target32'][a:b], torch.from_numpy((lptr[s0:s0 + nb + 1] - l0).astype(np.int32)).to(dev),
+                    L.eval_rank_lists(prec, emb, target, torch.from_numpy((lptr[s0:s0 + nb + 1] - l0).astype(np.int32)).to(dev),
                                       lflat[l0:l1 + 1], int(llens[s0:s0 + nb].max()), ptr, hist, rank)
                 elif cand is None:
-                    L.eval_rank(prec, emb, P['target32'][a:b], ptr, hist, rank)
+                    L.eval_rank(prec, emb, target, ptr, hist, rank)
                 else:
-                    L.eval_rank_cand(prec, emb, P['target32'][a:b], ptr, hist, cand, rank)
+                    L.eval_rank_cand(prec, emb, target, ptr, hist, cand, rank)
                 ranks.append(rank)
     if eval_negatives is not None:                                # not waited for: the caller reads it after its own synchronisation
         host = torch.zeros(1, dtype=torch.int32)
@@ -529,104 +468,56 @@ def eval_model(model, user_history, eval_seq, item_embeddings, test_batch_size, 
     ``eval_negatives`` (an EvalNegatives): every target is ranked among the negatives drawn for its user on the device -- the sampled protocol of
     the SASRec / IDRec papers -- and the means run over the users who had an item left to draw."""
     _both_refused(candidates, candidate_lists, eval_negatives)
-    if eval_negatives is not None:
-        return _eval_model_negatives(model, user_history, eval_seq, item_embeddings, test_batch_size, args, Log_file, v_or_t, eval_negatives)
-    if candidate_lists is not None:
-        return _eval_model_lists(model, user_history, eval_seq, item_embeddings, test_batch_size, args, Log_file, v_or_t, candidate_lists)
-    if candidates is not None:
-        return _eval_model_candidates(model, user_history, eval_seq, item_embeddings, test_batch_size, args, Log_file, v_or_t, candidates)
-    world = dist.get_world_size() if dist.is_initialized() else 1
-    rank_id = dist.get_rank() if dist.is_initialized() else 0
     n_users = len(eval_seq)
-    sampler = SequentialDistributedSampler(range(n_users), test_batch_size, rank=rank_id, num_replicas=world)
-    user_ids = sampler.indices()
-    model.eval()
-    topK = 10
-    Log_file.info(v_or_t + '_methods   {}'.format('\t'.join(['Hit{}'.format(topK), 'nDCG{}'.format(topK)])))
-    ranks = eval_ranks(model, user_history, eval_seq, item_embeddings, test_batch_size, args, user_ids).float()
-    hit = (ranks <= topK).float()
-    ndcg = torch.where(ranks <= topK, 1.0 / torch.log2(ranks + 1.0), torch.zeros_like(ranks))
-    if world > 1:
-        parts_h = [torch.zeros_like(hit) for _ in range(world)]
-        parts_n = [torch.zeros_like(ndcg) for _ in range(world)]
-        dist.all_gather(parts_h, hit)
-        dist.all_gather(parts_n, ndcg)
-        hit, ndcg = torch.cat(parts_h), torch.cat(parts_n)
-    mean_eval = [float(hit[:n_users].mean().item()), float(ndcg[:n_users].mean().item())]
-    print_metrics(mean_eval, Log_file, v_or_t)
-    return mean_eval[0]
-
-
-def _eval_model_candidates(model, user_history, eval_seq, item_embeddings, test_batch_size, args, Log_file, v_or_t, candidates):
-    """eval_model within a candidate set: the same sharding, log lines and gather, with a validity flag (the user's target is a candidate)
-    travelling beside hit and ndcg; the means are sums over the valid users divided by their number."""
-    world = dist.get_world_size() if dist.is_initialized() else 1
-    rank_id = dist.get_rank() if dist.is_initialized() else 0
-    n_users = len(eval_seq)
-    sampler = SequentialDistributedSampler(range(n_users), test_batch_size, rank=rank_id, num_replicas=world)
-    user_ids = sampler.indices()
+    world, _, user_ids = _shard_users(n_users, test_batch_size)
     model.eval()
     topK = 10
     dev = next(model.parameters()).device
     cand = candidate_mask(candidates, item_embeddings.shape[0], dev)          # uploaded once; eval_ranks takes it as it is
     Log_file.info(v_or_t + '_methods   {}'.format('\t'.join(['Hit{}'.format(topK), 'nDCG{}'.format(topK)])))
-    ranks = eval_ranks(model, user_history, eval_seq, item_embeddings, test_batch_size, args, user_ids, candidates=cand).float()
-    P = _prepare_eval_set(eval_seq, user_history, args.max_seq_len + 1, dev)
-    uid = torch.from_numpy(np.asarray(user_ids, dtype=np.int64)).to(dev)
-    valid = (cand[P['target'][uid]] != 0).float() if uid.numel() else torch.zeros(0, device=dev)
-    return _means_over_valid(ranks, valid, n_users, topK, world, Log_file, v_or_t, 'candidates', 'has a target among the candidate items')
-
-
-def _eval_model_lists(model, user_history, eval_seq, item_embeddings, test_batch_size, args, Log_file, v_or_t, candidate_lists):
-    """eval_model within each user's own candidate list: as _eval_model_candidates, the validity flag being "the user has a list"."""
-    world = dist.get_world_size() if dist.is_initialized() else 1
-    rank_id = dist.get_rank() if dist.is_initialized() else 0
-    n_users = len(eval_seq)
-    sampler = SequentialDistributedSampler(range(n_users), test_batch_size, rank=rank_id, num_replicas=world)
-    user_ids = sampler.indices()
-    model.eval()
-    topK = 10
-    dev = next(model.parameters()).device
-    Log_file.info(v_or_t + '_methods   {}'.format('\t'.join(['Hit{}'.format(topK), 'nDCG{}'.format(topK)])))
-    ranks = eval_ranks(model, user_history, eval_seq, item_embeddings, test_batch_size, args, user_ids, candidate_lists=candidate_lists).float()
-    valid = torch.from_numpy(has_candidate_list(candidate_lists, user_ids).astype(np.float32)).to(dev)
-    return _means_over_valid(ranks, valid, n_users, topK, world, Log_file, v_or_t, 'candidate_lists', 'has a candidate list')
-
-
-def _eval_model_negatives(model, user_history, eval_seq, item_embeddings, test_batch_size, args, Log_file, v_or_t, spec):
-    """eval_model on drawn negatives: as _eval_model_lists, the validity flag being "the user has an item left to draw" (computed from the
-    histories; the kernels' own count of such users, read after the synchronisation of the means, must agree)."""
-    world = dist.get_world_size() if dist.is_initialized() else 1
-    rank_id = dist.get_rank() if dist.is_initialized() else 0
-    n_users = len(eval_seq)
-    sampler = SequentialDistributedSampler(range(n_users), test_batch_size, rank=rank_id, num_replicas=world)
-    user_ids = sampler.indices()
-    model.eval()
-    topK = 10
-    dev = next(model.parameters()).device
-    Log_file.info(v_or_t + '_methods   {}'.format('\t'.join(['Hit{}'.format(topK), 'nDCG{}'.format(topK)])))
-    ranks = eval_ranks(model, user_history, eval_seq, item_embeddings, test_batch_size, args, user_ids, eval_negatives=spec).float()
-    P = _prepare_eval_set(eval_seq, user_history, args.max_seq_len + 1, dev)
-    valid = _negatives_valid(spec, P, user_ids, item_embeddings.shape[0], dev)
-    uid = np.asarray(user_ids, dtype=np.int64)
-    first = torch.from_numpy(np.concatenate([[True], np.diff(uid) != 0])).to(dev) if uid.size else torch.zeros(0, dtype=torch.bool, device=dev)
-    without = (1.0 - valid)[first].sum()                               # (the sampler's tail repeats the last user: counted once, as the kernel does)
-    hr = _means_over_valid(ranks, valid, n_users, topK, world, Log_file, v_or_t, 'eval_negatives', 'has an item left to draw')
-    if spec.last_err is not None and int(spec.last_err.item()) != int(without.item()):
-        raise RuntimeError(f'{v_or_t}: the kernels counted {int(spec.last_err.item())} users without a candidate, the histories give {int(without.item())}')
+    ranks = eval_ranks(model, user_history, eval_seq, item_embeddings, test_batch_size, args, user_ids, candidates=cand,
+                       candidate_lists=candidate_lists, eval_negatives=eval_negatives).float()
+    valid, label, what = _validity(user_history, eval_seq, item_embeddings.shape[0], args, user_ids, dev, cand, candidate_lists, eval_negatives)
+    hr = _means_over_valid(ranks, valid, n_users, topK, world, Log_file, v_or_t, label, what)
+    if eval_negatives is not None and eval_negatives.last_err is not None:
+        # the kernels' own count of the users without a candidate, read after the synchronisation of the means, must agree with the histories
+        uid = np.asarray(user_ids, dtype=np.int64)
+        first = torch.from_numpy(np.concatenate([[True], np.diff(uid) != 0])).to(dev) if uid.size else torch.zeros(0, dtype=torch.bool, device=dev)
+        without = int((1.0 - valid)[first].sum().item())              # (the sampler's tail repeats the last user: counted once, as the kernel does)
+        if int(eval_negatives.last_err.item()) != without:
+            raise RuntimeError(f'{v_or_t}: the kernels counted {int(eval_negatives.last_err.item())} users without a candidate, the histories give {without}')
     return hr
+
+
+def _validity(user_history, eval_seq, n1, args, user_ids, dev, cand, candidate_lists, eval_negatives):
+    """Which of the listed users eval_model's means run over under each restriction -> (float flags [len(user_ids)], the label of the
+    ``k of n users`` line, what a counted user has); (None, None, None) without a restriction: every user counts."""
+    if eval_negatives is not None:                                    # the user has an item left to draw (computed from the histories)
+        P = _prepare_eval_set(eval_seq, user_history, args.max_seq_len + 1, dev)
+        return _negatives_valid(eval_negatives, P, user_ids, n1, dev), 'eval_negatives', 'has an item left to draw'
+    if candidate_lists is not None:
+        valid = torch.from_numpy(has_candidate_list(candidate_lists, user_ids).astype(np.float32)).to(dev)
+        return valid, 'candidate_lists', 'has a candidate list'
+    if cand is not None:
+        P = _prepare_eval_set(eval_seq, user_history, args.max_seq_len + 1, dev)
+        uid = torch.from_numpy(np.asarray(user_ids, dtype=np.int64)).to(dev)
+        valid = (cand[P['target'][uid]] != 0).float() if uid.numel() else torch.zeros(0, device=dev)
+        return valid, 'candidates', 'has a target among the candidate items'
+    return None, None, None
 
 
 def _means_over_valid(ranks, valid, n_users, topK, world, Log_file, v_or_t, label, what):
     """Hit@topK / nDCG@topK as means over the users whose validity flag is set (gathered over the data-parallel group beside hit and ndcg), the
-    metrics line and ``<v_or_t>_<label>   k of n users``; ValueError when no user qualifies."""
-    hit = (ranks <= topK).float() * valid
-    ndcg = torch.where(ranks <= topK, 1.0 / torch.log2(ranks + 1.0), torch.zeros_like(ranks)) * valid
-    if world > 1:
-        parts = [[torch.zeros_like(t) for _ in range(world)] for t in (hit, ndcg, valid)]
-        for p, t in zip(parts, (hit, ndcg, valid)):
-            dist.all_gather(p, t)
-        hit, ndcg, valid = (torch.cat(p) for p in parts)
+    metrics line and ``<v_or_t>_<label>   k of n users``; ValueError when no user qualifies.  ``valid`` None (no restriction): the means over all
+    users, and no such line."""
+    hit = (ranks <= topK).float()
+    ndcg = torch.where(ranks <= topK, 1.0 / torch.log2(ranks + 1.0), torch.zeros_like(ranks))
+    if valid is None:             # the reference's fp32 .mean(), not sum / n_users: the two differ in the last bits, so this branch is not folded into the other
+        hit, ndcg = _gather_cat(hit, world), _gather_cat(ndcg, world)
+        mean_eval = [float(hit[:n_users].mean().item()), float(ndcg[:n_users].mean().item())]
+        print_metrics(mean_eval, Log_file, v_or_t)
+        return mean_eval[0]
+    hit, ndcg, valid = (_gather_cat(t, world) for t in (hit * valid, ndcg * valid, valid))
     k = int(valid[:n_users].sum().item())
     if k == 0:
         raise ValueError(f'{v_or_t}: no user of {n_users} {what}')
@@ -645,22 +536,12 @@ def _recommend_inputs(user_seqs, exclude, uids, T):
     lens = np.fromiter((len(s) for s in seqs), dtype=np.int64, count=n)
     if n and int(lens.min()) == 0:
         raise ValueError(f'user {int(uids[int(lens.argmin())])}: an empty sequence has nothing to recommend from')
-    rows = np.repeat(np.arange(n), lens)
-    cols = (np.arange(int(lens.sum())) - np.repeat(np.cumsum(lens) - lens, lens)) + np.repeat(T - lens, lens)
-    ids = np.zeros((n, T), dtype=np.int64)
-    mask = np.zeros((n, T), dtype=np.float32)
-    ids[rows, cols] = np.fromiter(itertools.chain.from_iterable(seqs), dtype=np.int64, count=int(lens.sum()))
-    mask[rows, cols] = 1.0
+    ids, mask = _left_pad(np.fromiter(itertools.chain.from_iterable(seqs), dtype=np.int64, count=int(lens.sum())), lens, T)
     ex = [np.asarray(exclude[int(u)]).reshape(-1).astype(np.int64) for u in uids] if exclude is not None else [np.asarray(user_seqs[int(u)], dtype=np.int64).reshape(-1) for u in uids]
-    el = np.fromiter((e.size for e in ex), dtype=np.int64, count=n)
+    ptr, flat, el = _csr_int32(ex)
     if n and int(el.max()) > L.EVAL_MAX_HISTORY:              # never truncate: an unexcluded item would be recommended silently
         u = int(el.argmax())
         raise ValueError(f'user {int(uids[u])}: exclusion list of {int(el[u])} items exceeds A4R_EVAL_MAX_HISTORY = {L.EVAL_MAX_HISTORY}')
-    ptr = np.zeros(n + 1, dtype=np.int64)
-    np.cumsum(el, out=ptr[1:])
-    flat = np.concatenate(ex + [np.zeros(1, np.int64)])
-    # ids outside int32 can never name a table row; clamp them to -1 (ignored like any id outside 1 .. N1-1) instead of letting them wrap
-    flat = np.where((flat < 0) | (flat > np.iinfo(np.int32).max), -1, flat).astype(np.int32)
     return ids, mask, ptr, flat
 
 
@@ -754,26 +635,17 @@ def write_recommendations(model, user_seqs, user_history, item_embeddings, k, ba
     ``diversify``: as recommend's.  The file's format is unchanged; a line's scores are the items' relevance scores in the order the items were
     picked, no longer necessarily descending.  ``Log_file`` then gets one line, ``recommend_ild``: the mean intra-list diversity (mean 1 - cosine
     over a list's pairs of items) of the plain top-k lists and of the re-ranked ones, over the users with at least two items (``k of n users``)."""
-    world = dist.get_world_size() if dist.is_initialized() else 1
-    rank_id = dist.get_rank() if dist.is_initialized() else 0
     n_users = len(user_seqs)
-    uids = SequentialDistributedSampler(range(n_users), batch_size, rank=rank_id, num_replicas=world).indices()
+    world, rank_id, uids = _shard_users(n_users, batch_size)
     exclude = {}
     for u in uids:
         u = int(u)
         if u not in exclude:
             exclude[u] = np.concatenate([np.asarray(user_history[u], dtype=np.int64).reshape(-1), np.asarray(user_seqs[u][-1:], dtype=np.int64)])
     ids, scores, ild = _recommend(model, user_seqs, item_embeddings, k, args, exclude, uids, candidates, candidate_lists, diversify, True)
-    if world > 1:
-        parts_i = [torch.zeros_like(ids) for _ in range(world)]
-        parts_s = [torch.zeros_like(scores) for _ in range(world)]
-        dist.all_gather(parts_i, ids)
-        dist.all_gather(parts_s, scores)
-        ids, scores = torch.cat(parts_i), torch.cat(parts_s)
-        if ild is not None:                                        # gathered over the ranks the way the ids are
-            parts_d = [torch.zeros_like(ild) for _ in range(world)]
-            dist.all_gather(parts_d, ild)
-            ild = torch.cat(parts_d)
+    ids, scores = _gather_cat(ids, world), _gather_cat(scores, world)
+    if ild is not None:                                            # gathered over the ranks the way the ids are
+        ild = _gather_cat(ild, world)
     if rank_id != 0:
         return None
     ids, scores = ids[:n_users].cpu().numpy(), scores[:n_users].cpu().numpy()

@@ -18,9 +18,7 @@ from torch.utils.data import DataLoader
 
 from .data_utils import (BuildTrainDataset, eval_model, get_doc_input_bert, get_item_embeddings, read_behaviors,
                          read_news_bert)
-from .data_utils.metrics import (check_eval_negatives_flag, eval_negatives_from_args, write_eval_negatives, candidate_lists_from_args, candidate_mask, candidates_from_args, check_candidate_flag, check_diversify_flag, diversify_from_args, read_candidate_lists, read_candidates,
-                                 write_recommendations)
-from .data_utils.preprocess import read_behavior_names
+from .data_utils.eval_flags import check_flags, eval_restriction, write_recommend_mode
 from .data_utils.dataset import DeviceTrainSampler
 from .data_utils.utils import (get_checkpoint, para_and_log, report_time_eval, report_time_train, save_model, setuplogger)
 from .ddp import FlatDDP, any_rank
@@ -91,16 +89,12 @@ def build_model(args, item_num, use_modal, bert_model, local_rank, Log_file, mod
     return model.to(local_rank), start_epoch, ckpt2
 
 
-def run_eval_once(model, item_content, user_history, users_eval, batch_size, item_num, use_modal, mode, local_rank, args, Log_file, candidates=None, candidate_lists=None, eval_negatives=None):
+def run_eval_once(model, item_content, user_history, users_eval, batch_size, item_num, use_modal, mode, local_rank, args, Log_file, **restriction):
+    """``restriction``: eval_model's candidates / candidate_lists / eval_negatives, as eval_flags.eval_restriction gives them"""
     t0 = time.time()
     Log_file.info('Validating...')
     emb = get_item_embeddings(model, item_content, batch_size, args, use_modal, local_rank)
-    kw = {} if candidates is None else dict(candidates=candidates)      # --candidate_items: ranked among, and averaged over targets within, the candidate set
-    if candidate_lists is not None:                                     # --candidate_lists: ranked within the user's own list, averaged over the users who have one
-        kw = dict(candidate_lists=candidate_lists)
-    if eval_negatives is not None:                                      # --eval_negatives: ranked among negatives drawn on the device, averaged over the users who have a candidate
-        kw = dict(eval_negatives=eval_negatives)
-    hit10 = eval_model(model, user_history, users_eval, emb, batch_size, args, item_num, Log_file, mode, local_rank, **kw)
+    hit10 = eval_model(model, user_history, users_eval, emb, batch_size, args, item_num, Log_file, mode, local_rank, **restriction)
     report_time_eval(t0, Log_file)
     return hit10
 
@@ -136,8 +130,9 @@ def train(args, use_modal, local_rank, Log_file, Log_screen, model_dir, start_ti
                 items, mask = dev_sampler.sample(ids[i:i + args.batch_size])
                 yield items.view(-1, args.max_seq_len + 1, 2, items.size(-1)), mask
     model = FlatDDP(model, device_ids=[local_rank], output_device=local_rank)
-    neg = eval_negatives_from_args(args, users_train, item_num, Log_file)
-    ekw = {} if neg is None else dict(eval_negatives=neg)             # --eval_negatives; without the flag the calls are the ones made before
+    # --eval_negatives (the only restriction training takes); without the flag the calls are the ones made before
+    ekw = eval_restriction(args, os.path.join(args.root_data_dir, args.dataset, args.behaviors), before_name2id, users_train, hist_test, users_test,
+                           item_num, next(model.parameters()).device, Log_file)
     optimizer = optimizer_from_args(optimizer_groups(model, args), args)      # --optimizer / --weight_decay / --max_grad_norm; default: FusedAdam
     if ckpt2 is not None:
         optimizer.load_state_dict(ckpt2['optimizer'])
@@ -203,27 +198,10 @@ def test(args, use_modal, local_rank, Log_file, Log_screen, model_dir, start_tim
     item_content = np.concatenate([x for x in get_doc_input_bert(id2dic, args) if x is not None], axis=1)
     model, _, _ = build_model(args, item_num, use_modal, bert_model, local_rank, Log_file, model_dir)
     model = FlatDDP(model, device_ids=[local_rank], output_device=local_rank)
-    cand = candidates_from_args(args, os.path.join(args.root_data_dir, args.dataset, args.behaviors), before_name2id, Log_file)
-    # --candidate_items: the mask is uploaded once, for both splits; without the flag the calls are the ones made before
-    kw = {} if cand is None else dict(candidates=candidate_mask(cand, item_num + 1, next(model.parameters()).device))
-    lists = candidate_lists_from_args(args, os.path.join(args.root_data_dir, args.dataset, args.behaviors), before_name2id, Log_file)
-    if lists is not None:                                              # --candidate_lists (never beside --candidate_items: main refuses the pair)
-        kw = dict(candidate_lists=lists)
-    neg = eval_negatives_from_args(args, users_train, item_num, Log_file)
-    if neg is not None:                                                # --eval_negatives (never beside either candidate flag: main refuses the pair)
-        kw = dict(eval_negatives=neg)
-        if args.eval_negatives_out and dist.get_rank() == 0:
-            user_names, item_names = read_behavior_names(os.path.join(args.root_data_dir, args.dataset, args.behaviors), before_name2id,
-                                                         args.max_seq_len, args.min_seq_len)
-            k = write_eval_negatives(neg, hist_test, users_test, item_num + 1, args, user_names, item_names, args.eval_negatives_out,
-                                     next(model.parameters()).device)
-            Log_file.info(f'eval negatives: the draws of the test split for {k} users -> {args.eval_negatives_out}')
+    kw = eval_restriction(args, os.path.join(args.root_data_dir, args.dataset, args.behaviors), before_name2id, users_train, hist_test, users_test,
+                          item_num, next(model.parameters()).device, Log_file)
     run_eval_once(model, item_content, hist_valid, users_valid, 512, item_num, use_modal, 'valid', local_rank, args, Log_file, **kw)
     run_eval_once(model, item_content, hist_test, users_test, 512, item_num, use_modal, 'test', local_rank, args, Log_file, **kw)
-
-
-def recommend_out_path(args, model_dir):
-    return args.recommend_out or os.path.join(model_dir, f'recommend_{args.load_ckpt_name}.tsv')
 
 
 def recommend(args, use_modal, local_rank, Log_file, Log_screen, model_dir, start_time):
@@ -233,17 +211,11 @@ def recommend(args, use_modal, local_rank, Log_file, Log_screen, model_dir, star
     path = os.path.join(args.root_data_dir, args.dataset, args.behaviors)
     before_id2dic, before_name2id = read_news_bert(os.path.join(args.root_data_dir, args.dataset, args.news), args, tokenizer)
     item_num, id2dic, _, _, users_test, _, hist_test = read_behaviors(path, before_id2dic, before_name2id, args.max_seq_len, args.min_seq_len, Log_file)
-    user_names, item_names = read_behavior_names(path, before_name2id, args.max_seq_len, args.min_seq_len)
     item_content = np.concatenate([x for x in get_doc_input_bert(id2dic, args) if x is not None], axis=1)
     model, _, _ = build_model(args, item_num, use_modal, bert_model, local_rank, Log_file, model_dir)
     model = FlatDDP(model, device_ids=[local_rank], output_device=local_rank)
     emb = get_item_embeddings(model, item_content, 512, args, use_modal, local_rank)
-    out = write_recommendations(model, users_test, hist_test, emb, args.topk, 512, args, user_names, item_names, recommend_out_path(args, model_dir),
-                                candidates=read_candidates(args.candidate_items, item_names) if args.candidate_items else None,
-                                candidate_lists=read_candidate_lists(args.candidate_lists, user_names, item_names) if args.candidate_lists else None,
-                                diversify=diversify_from_args(args, Log_file), Log_file=Log_file)
-    if out:
-        Log_file.info(f'recommend: top-{args.topk} lists of {len(users_test)} users -> {out}')
+    write_recommend_mode(args, model, users_test, hist_test, emb, 512, path, before_name2id, model_dir, Log_file)
 
 
 def setup_seed(seed):
@@ -255,9 +227,7 @@ def setup_seed(seed):
 
 def main(argv=None):
     args = parse_args(argv)
-    check_candidate_flag(args)
-    check_eval_negatives_flag(args)
-    check_diversify_flag(args)
+    check_flags(args)
     local_rank = args.local_rank if args.local_rank >= 0 else int(os.environ.get('LOCAL_RANK', 0))
     torch.cuda.set_device(local_rank)
     dist.init_process_group(backend='nccl', init_method='env://')      # 'nccl' is RCCL on ROCm

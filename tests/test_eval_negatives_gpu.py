@@ -289,7 +289,8 @@ def test_eval_model_with_eval_negatives_on_an_id_model(sampling, monkeypatch, tm
     from test_topk_gpu import _id_model
     from adapter4rec_amd import _lib as L
     from adapter4rec_amd.cv.data_utils import get_itemId_embeddings
-    from adapter4rec_amd.data_utils.metrics import (eval_model, eval_negatives_from_args, eval_ranks, read_candidate_lists, write_eval_negatives)
+    from adapter4rec_amd.data_utils.eval_flags import eval_negatives_from_args
+    from adapter4rec_amd.data_utils.metrics import (eval_model, eval_ranks, read_candidate_lists, write_eval_negatives)
     model, args, item_num = _id_model()
     emb = get_itemId_embeddings(model, item_num, 256, args, 0)
     N1, E = emb.shape

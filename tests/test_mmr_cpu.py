@@ -246,7 +246,8 @@ def test_flag_refusals():
     """Before anything is set up (no device, no process group)."""
     from adapter4rec_amd import run
     from adapter4rec_amd.cv import run_adapter
-    from adapter4rec_amd.data_utils.metrics import Diversify, check_diversify_flag
+    from adapter4rec_amd.data_utils.eval_flags import check_diversify_flag
+    from adapter4rec_amd.data_utils.metrics import Diversify
     from adapter4rec_amd.parameters import parse_args
     for main in (run.main, run_adapter.main):
         for mode in ('train', 'test'):
