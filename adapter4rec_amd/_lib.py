@@ -954,6 +954,8 @@ SATELLITES = {
     '_lib_eval_negatives': ('EVAL_NEGATIVES_SIGNATURES', ('EVAL_NEG_SITE', 'EVAL_NEG_MAX', 'eval_draw_negatives', 'eval_rank_sampled')),
     # the diversified re-ranking of a top-K list: include/a4r_diversify.h
     '_lib_diversify': ('DIVERSIFY_SIGNATURES', ('MMR_MAX_POOL', 'mmr_rerank')),
+    # similar items, every query item's nearest items of the table: include/a4r_similar.h
+    '_lib_similar': ('SIMILAR_SIGNATURES', ('row_inv_norms', 'topk_similar')),
 }
 
 

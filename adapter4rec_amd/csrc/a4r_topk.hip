@@ -15,6 +15,9 @@
 // listed key's final position is its position in its own list plus the number of keys above it in the others (binary searches in LDS; keys are
 // unique, so positions are distinct).  Keys are a total order and each item range holds every item of the global top K that falls in it, so
 // the result does not depend on the grid.
+//
+// Similar items (a4r_topk_similar, include/a4r_similar.h).  similar_partial_kernel is the same sweep and selection with the 16 rows of a workgroup
+// taken from the item table itself; compaction, merge and decode are the ones above, shared as they are.  a4r_row_inv_norms lives here too.
 #include "a4r_score_sweep.h"
 #include "a4r_topk_key.h"
 #include "../../include/a4r.h"
@@ -147,6 +150,104 @@ __global__ void __launch_bounds__(256) topk_partial_kernel(const float* __restri
     }
 }
 
+// Similar items (a4r_topk_similar, include/a4r_similar.h): topk_partial_kernel with the 16 rows of a workgroup taken from the table itself.  The A
+// fragments are loaded straight from item_emb[query[..]] (no gather); one compare i == q stands where the exclusion list, its LDS and its sorting
+// prologue were.  COS is the cosine metric (inv non-null): score = dot * (inv[q] * inv[i]); inv[i] of the lane's item column is requested with that
+// tile's fragments, one tile ahead, and the inv[q] of the lane's four accumulator rows stay in registers.  A row whose query id is no item
+// (or has inv[q] == 0) is dead: it adds no key, and its fragments come from row 0.
+template <int E, bool CAND, bool COS>
+__global__ void __launch_bounds__(256) similar_partial_kernel(const float* __restrict__ item_emb, const float* __restrict__ inv,
+                                                              const int32_t* __restrict__ query, const uint8_t* __restrict__ cand, float min_sim,
+                                                              uint64_t* __restrict__ ws, int Q, int N1, int K, int cap) {
+    constexpr int KS = E / 16;
+    extern __shared__ uint64_t buf[];                // [16][cap] candidate keys
+    __shared__ int32_t cnt[16];
+    __shared__ uint64_t thr_s[16];
+    __shared__ int trig;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int r16 = lane & 15, kg = lane >> 4;
+    const int u0 = blockIdx.x * 16;
+    constexpr bool cosine = COS;                     // (a template argument: as a run-time branch beside the request-ahead loads it cost 15 - 60 registers)
+    if (tid < 16) { cnt[tid] = 0; thr_s[tid] = 0; }
+    if (tid == 0) trig = -1;
+    uint4 ua[KS];                                    // A operand: the 16 query rows
+    {
+        const int q = query[min(u0 + r16, Q - 1)];
+        frag_load<E>(ua, item_emb, (q >= 1 && q < N1) ? q : 0, kg);
+    }
+    int qid[4];                                      // the query ids of this lane's accumulator rows, 0 = dead
+    float iq[4];
+#pragma unroll
+    for (int rr = 0; rr < 4; ++rr) {
+        const int r = u0 + kg * 4 + rr;
+        const int q = query[min(r, Q - 1)];
+        const bool ok = r < Q && q >= 1 && q < N1;
+        iq[rr] = (ok && cosine) ? inv[q] : 1.f;
+        qid[rr] = (ok && iq[rr] != 0.f) ? q : 0;
+    }
+    __syncthreads();
+    const SweepDeal<> deal(N1, wave);
+    const int nsteps = deal.steps();                 // the 4 waves meet at every step's barrier
+    uint64_t thr[4] = {0, 0, 0, 0};
+    int t = deal.first;
+    uint4 bn[KS];
+    sweep_begin<E, true>(bn, item_emb, deal, r16, kg);
+    float ivn = cosine ? inv[deal.row(deal.first, r16)] : 1.f;
+    for (int s = 0; s < nsteps; ++s, t += deal.tstep) {
+        const int i = 1 + t * 16 + r16;                 // this lane's item column (>= N1 past the end of the table: nothing to add)
+        uint4 b[KS];
+        const float iv = ivn;
+        sweep_next<E, true>(b, bn, item_emb, deal, t, r16, kg);
+        if (cosine) ivn = inv[deal.row(t + deal.tstep, r16)];
+        const f32x4_t acc = score_tile<float>(ua, b);
+        const bool col = i < N1 && iv != 0.f;           // (dot metric: iv = 1)
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) {
+            const float sc = cosine ? acc[rr] * (iq[rr] * iv) : acc[rr];
+            const uint64_t key = topk_key(sc, i);
+            if (col && qid[rr] != 0 && i != qid[rr] && sc >= min_sim && key > thr[rr]) {
+                if constexpr (CAND)
+                    if (cand[i] == 0) continue;
+                const int ul = kg * 4 + rr;
+                const int p = atomicAdd(&cnt[ul], 1);
+                buf[ul * cap + p] = key;
+                if (p >= cap - STEP_KEYS) trig = s;          // (as in topk_partial_kernel)
+            }
+        }
+        __syncthreads();
+        if (trig == s) {
+            topk_compact(buf, cap, K, cnt, thr_s);
+#pragma unroll
+            for (int rr = 0; rr < 4; ++rr) thr[rr] = thr_s[kg * 4 + rr];
+        }
+    }
+    topk_compact(buf, cap, K, cnt, thr_s);
+    for (int e = tid; e < 16 * K; e += 256) {
+        const int ul = e / K, j = e - ul * K;
+        if (u0 + ul < Q) ws[((size_t)blockIdx.y * Q + u0 + ul) * K + j] = buf[ul * cap + j];
+    }
+}
+
+// a4r_row_inv_norms: 16 lanes per row; a lane squares and sums its 16-byte chunks j, j + 16, ... in fp64, then a butterfly over the row's lanes
+template <int E>
+__global__ void __launch_bounds__(256) row_inv_norms_kernel(const float* __restrict__ table, float* __restrict__ inv, int N1) {
+    const int j = threadIdx.x & 15;
+    const int64_t row = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4);
+    const int64_t r = row < N1 ? row : N1 - 1;
+    double s = 0.0;
+#pragma unroll
+    for (int c = 0; c < E / 64; ++c) {
+        const float4 v = *reinterpret_cast<const float4*>(table + r * E + (c * 16 + j) * 4);
+        s += (double)v.x * (double)v.x;
+        s += (double)v.y * (double)v.y;
+        s += (double)v.z * (double)v.z;
+        s += (double)v.w * (double)v.w;
+    }
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    if (j == 0 && row < N1) inv[row] = (s > 0.0 && s < __builtin_huge_val()) ? (float)(1.0 / sqrt(s)) : 0.f;      // (NaN fails both compares)
+}
+
 // one item range: the workgroup's sorted list is the answer
 __global__ void topk_decode_kernel(const uint64_t* __restrict__ ws, int32_t* __restrict__ ids, float* __restrict__ scores, int64_t n) {
     for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256) topk_emit(ws[e], ids + e, scores + e);
@@ -226,7 +327,54 @@ int topk_launch(void* stream, const float* prec, const float* item_emb, const in
     return a4r_launch_status();
 }
 
+// a4r_topk_similar's launches: the partial kernel above over top-K's grid with U = Q, then top-K's own decode or merge
+template <bool CAND, bool COS>
+int similar_launch(hipStream_t s, const float* item_emb, const float* inv, const int32_t* query, const uint8_t* cand, float min_sim, int32_t* ids,
+                   float* scores, uint64_t* w, int Q, int N1, int E, int K) {
+    const int gy = topk_ranges(Q, N1), cap = topk_cap(K);
+    const dim3 grid((Q + 15) / 16, gy);
+    const size_t lds = (size_t)16 * cap * sizeof(uint64_t);
+    int rc = A4R_OK;
+    with_width(WidthsF32{}, E, [&](auto e) {
+        const auto kernel = similar_partial_kernel<decltype(e)::value, CAND, COS>;
+        if ((rc = a4r_set_lds(kernel, lds))) return;
+        hipLaunchKernelGGL(kernel, grid, dim3(256), lds, s, item_emb, inv, query, cand, min_sim, w, Q, N1, K, cap);
+    });
+    if (rc) return rc;
+    if (gy == 1) {
+        const int64_t n = (int64_t)Q * K;
+        const int blocks = (int)((n + 255) / 256 < 8192 ? (n + 255) / 256 : 8192);
+        hipLaunchKernelGGL(topk_decode_kernel, dim3(blocks), dim3(256), 0, s, w, ids, scores, n);
+    } else {
+        const size_t mlds = (size_t)gy * K * sizeof(uint64_t);
+        if ((rc = a4r_set_lds(topk_merge_kernel, mlds))) return rc;
+        hipLaunchKernelGGL(topk_merge_kernel, dim3(Q), dim3(256), mlds, s, w, ids, scores, Q, K, gy);
+    }
+    return a4r_launch_status();
+}
+
 }  // namespace
+
+extern "C" int a4r_row_inv_norms(void* stream, const float* table, float* inv, int N1, int E) {
+    if (!table || !inv || N1 < 1 || !width_served(WidthsF32{}, E) || !aligned16(table, nullptr)) return A4R_EINVAL;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    with_width(WidthsF32{}, E, [&](auto e) {
+        hipLaunchKernelGGL(row_inv_norms_kernel<decltype(e)::value>, dim3((N1 + 15) / 16), dim3(256), 0, s, table, inv, N1);
+    });
+    return a4r_launch_status();
+}
+
+extern "C" int a4r_topk_similar(void* stream, const float* item_emb, const float* inv_norm, const int32_t* query, const uint8_t* cand,
+                                float min_sim, int32_t* ids, float* scores, void* ws, int Q, int N1, int E, int K) {
+    if (!item_emb || !query || !ids || !scores || !ws || !topk_shape_ok(Q, N1, K) || min_sim != min_sim) return A4R_EINVAL;
+    if (!width_served(WidthsF32{}, E) || !aligned16(item_emb, nullptr)) return A4R_EINVAL;
+    if (reinterpret_cast<uintptr_t>(ws) & 7u) return A4R_EINVAL;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    uint64_t* w = static_cast<uint64_t*>(ws);
+    const auto launch = cand ? (inv_norm ? similar_launch<true, true> : similar_launch<true, false>)
+                             : (inv_norm ? similar_launch<false, true> : similar_launch<false, false>);
+    return launch(s, item_emb, inv_norm, query, cand, min_sim, ids, scores, w, Q, N1, E, K);
+}
 
 extern "C" size_t a4r_topk_ws_bytes(int U, int N1, int K) {
     if (!topk_shape_ok(U, N1, K)) return 0;

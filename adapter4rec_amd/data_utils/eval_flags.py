@@ -1,6 +1,6 @@
-"""The flags that restrict or re-rank what evaluation and recommendation range over (--topk .. --eval_negatives_out), for both entry points
-(run.py, cv/run_adapter.py): their declaration, their refusals, and their translation into the arguments of data_utils.metrics (eval_model's
-restriction, write_recommendations' call).  No kernel is called from here."""
+"""The flags that restrict or re-rank what evaluation and recommendation range over (--topk .. --eval_negatives_out) and those of --mode similar
+(--similar_*), for both entry points (run.py, cv/run_adapter.py): their declaration, their refusals, and their translation into the arguments of
+data_utils.metrics (eval_model's restriction, write_recommendations' and write_similar_items' calls).  No kernel is called from here."""
 import math
 import os
 
@@ -8,8 +8,8 @@ import torch.distributed as dist
 
 from .._lib_diversify import MMR_MAX_POOL
 from .._lib_user_lists import LIST_MAX
-from .metrics import (Diversify, EvalNegatives, candidate_mask, item_counts, read_candidate_lists, read_candidates, write_eval_negatives,
-                      write_recommendations)
+from .metrics import (SIMILAR_METRICS, Diversify, EvalNegatives, candidate_mask, item_counts, read_candidate_lists, read_candidates,
+                      read_similar_items, write_eval_negatives, write_recommendations, write_similar_items)
 from .preprocess import read_behavior_names
 
 
@@ -25,6 +25,10 @@ def add_eval_flags(p):
     p.add_argument('--eval_neg_sampling', type=str, default='uniform', choices=['uniform', 'pop'])      # pop: in proportion to an item's occurrences in the training sequences
     p.add_argument('--eval_neg_seed', type=int, default=20240607)      # the seed of the draws: the same negatives in every epoch, batch size and world size
     p.add_argument('--eval_negatives_out', type=str, default=None)     # --mode test: write the test split's drawn negatives as a --candidate_lists file
+    p.add_argument('--similar_out', type=str, default=None)            # --mode similar: output file (default <model_dir>/similar_<load_ckpt_name>.tsv)
+    p.add_argument('--similar_items', type=str, default=None)          # --mode similar: a file of item names, one per line -- the query items, in file order (default: every item)
+    p.add_argument('--similar_metric', type=str, default='cos', choices=list(SIMILAR_METRICS))      # --mode similar: cosine, or the dot product --mode recommend ranks by
+    p.add_argument('--similar_min', type=float, default=None)          # --mode similar: list only the items scoring at least this (0.95 under cos: near-duplicates)
 
 
 def check_flags(args):
@@ -32,6 +36,26 @@ def check_flags(args):
     check_candidate_flag(args)
     check_eval_negatives_flag(args)
     check_diversify_flag(args)
+    check_similar_flag(args)
+
+
+def check_similar_flag(args):
+    """--mode similar lists items, not users: the flags of per-user restriction, re-ranking and evaluation are refused under it instead of
+    ignored (--candidate_items is honoured: neighbours come from the set), and --similar_out / --similar_items / --similar_metric /
+    --similar_min are refused under every other mode."""
+    if args.mode != 'similar':
+        for flag, default in (('similar_out', None), ('similar_items', None), ('similar_metric', 'cos'), ('similar_min', None)):
+            if getattr(args, flag, default) != default:
+                raise ValueError(f'--{flag} is honoured by --mode similar only, not by --mode {args.mode}')
+        return
+    if getattr(args, 'candidate_lists', None):
+        raise ValueError('--candidate_lists is a list per user: it is not honoured by --mode similar (--candidate_items is)')
+    if getattr(args, 'diversify', 'none') != 'none':
+        raise ValueError(f'--diversify {args.diversify} re-ranks the lists of users: it is not honoured by --mode similar')
+    if int(getattr(args, 'eval_negatives', 0) or 0) != 0:
+        raise ValueError('--eval_negatives is an evaluation protocol: it is not honoured by --mode similar')
+    if args.similar_min is not None and math.isnan(float(args.similar_min)):
+        raise ValueError('--similar_min nan: not a number')
 
 
 def check_candidate_flag(args):
@@ -39,7 +63,7 @@ def check_candidate_flag(args):
     restricted by them, so any other mode refuses either flag instead of ignoring it.  The two together are refused as well: a user's own list
     is the restriction, not one more beside a shared set."""
     for flag in ('candidate_items', 'candidate_lists'):
-        if getattr(args, flag, None) and not ('test' in args.mode or args.mode == 'recommend'):
+        if getattr(args, flag, None) and not ('test' in args.mode or args.mode in ('recommend', 'similar')):
             raise ValueError(f'--{flag} is honoured by --mode test and --mode recommend only, not by --mode {args.mode} '
                              '(training and its per-epoch evaluation range over the whole catalogue)')
     if getattr(args, 'candidate_items', None) and getattr(args, 'candidate_lists', None):
@@ -149,3 +173,21 @@ def write_recommend_mode(args, model, users_test, hist_test, item_embeddings, ba
                                 recommend_out_path(args, model_dir), candidates=mask, candidate_lists=lists, diversify=spec, Log_file=Log_file)
     if out:
         Log_file.info(f'recommend: top-{args.topk} lists of {len(users_test)} users -> {out}')
+
+
+def similar_out_path(args, model_dir):
+    return args.similar_out or os.path.join(model_dir, f'similar_{args.load_ckpt_name}.tsv')
+
+
+def write_similar_mode(args, item_embeddings, batch_size, behaviors_path, name2id, model_dir, Log_file):
+    """The tail of --mode similar in both entry points: the --topk nearest items of every item (or of --similar_items' items, in file order) by
+    --similar_metric, within --candidate_items and not below --similar_min, written by rank 0 to --similar_out under the names of the item
+    file.  No user is encoded."""
+    _, item_names = read_behavior_names(behaviors_path, name2id, args.max_seq_len, args.min_seq_len)
+    mask, _ = _candidates_from_args(args, None, item_names, Log_file)
+    query = None
+    if getattr(args, 'similar_items', None):
+        query = read_similar_items(args.similar_items, item_names)
+        Log_file.info(f'similar items: {query.size} of {len(item_names) - 1} from {args.similar_items}')
+    write_similar_items(item_embeddings, args.topk, batch_size, item_names, similar_out_path(args, model_dir), item_ids=query, candidates=mask,
+                        metric=args.similar_metric, min_sim=args.similar_min, Log_file=Log_file)

@@ -664,3 +664,100 @@ def write_recommendations(model, user_seqs, user_history, item_embeddings, k, ba
             f.write(user_names[u] + '\t' + ' '.join(item_names[int(i)] for i in ids[u][keep]) + '\t'
                     + ' '.join('%.9g' % float(s) for s in scores[u][keep]) + '\n')
     return path
+
+
+def read_similar_items(path, item_names):
+    """A --similar_items file -> int64 array of item ids, in file order: one item name per line (``item_names`` as read_candidates').  Blank lines
+    and repeats are ignored (a repeated name keeps its first place); names that are no item raise ValueError listing the first few, as
+    read_candidates does; a file without any name raises as well."""
+    index = {name: i for i, name in enumerate(item_names) if i > 0 and name is not None}
+    ids, seen, unknown = [], set(), []
+    with open(path) as f:
+        for line in f:
+            name = line.strip()
+            if not name:
+                continue
+            i = index.get(name)
+            if i is None:
+                if name not in unknown:
+                    unknown.append(name)
+            elif i not in seen:
+                seen.add(i)
+                ids.append(i)
+    if unknown:
+        raise ValueError(f'{path}: {len(unknown)} name(s) that are no item of this dataset: ' + ', '.join(unknown[:5]) + (' ...' if len(unknown) > 5 else ''))
+    if not ids:
+        raise ValueError(f'{path}: no item name in the file')
+    return np.asarray(ids, dtype=np.int64)
+
+
+SIMILAR_METRICS = ('cos', 'dot')
+
+
+def similar_items(item_embeddings, k, item_ids=None, candidates=None, metric='cos', min_sim=None):
+    """The k nearest other items of the table for each query item.
+
+    ``item_embeddings``: the fp32 [N + 1, E] table of ``get_item_embeddings`` / ``get_itemLMDB_embeddings`` / ``get_itemId_embeddings`` (row 0 =
+    the pad item).  ``item_ids`` (default: 1 .. N): the query items, in the order of the returned rows; an id outside 1 .. N gets pad slots only,
+    a repeated id an equal row.  ``metric``: 'cos' (the cosine; an all-zero or non-finite row is no one's neighbour and has none) or 'dot' (the
+    scores --mode recommend ranks by).  ``candidates`` (candidate_mask's input): neighbours come from the candidate items only; a query need not
+    be one.  ``min_sim``: items scoring below it are not listed (0.95 under 'cos': near-duplicates only).
+    Returns (ids LongTensor [Q, k], scores fp32 [Q, k]) on the table's device: score descending, ties by smaller id, the query itself never
+    listed; fewer than k neighbours: id 0 / score -inf in the remaining slots.  The rule: include/a4r_similar.h.  One a4r_topk_similar launch pair
+    per batch of A4R_EVAL_USER_BATCH (default 8192) queries, the inverse norms computed once per call (a4r_row_inv_norms); neither a normalised
+    copy of the table nor the [queries, items] score matrix is formed."""
+    if metric not in SIMILAR_METRICS:
+        raise ValueError(f'similar_items: metric {metric!r}, expected one of {SIMILAR_METRICS}')
+    if min_sim is not None and math.isnan(float(min_sim)):
+        raise ValueError('similar_items: min_sim is NaN')
+    k = int(k)
+    emb = item_embeddings.float().contiguous()
+    dev = emb.device
+    n1 = emb.shape[0]
+    cand = candidate_mask(candidates, n1, dev)
+    q = np.arange(1, n1, dtype=np.int64) if item_ids is None else np.asarray(torch.as_tensor(item_ids).cpu(), dtype=np.int64).reshape(-1)
+    if q.size == 0:
+        return torch.zeros(0, k, dtype=torch.long, device=dev), torch.zeros(0, k, dtype=torch.float32, device=dev)
+    q32 = torch.from_numpy(np.where((q < 0) | (q > np.iinfo(np.int32).max), 0, q).astype(np.int32)).to(dev)      # (an id outside int32 names no row: a pad list)
+    inv = L.row_inv_norms(emb) if metric == 'cos' else None
+    step = int(os.environ.get('A4R_EVAL_USER_BATCH', 0)) or 8192          # (eval_ranks' user batch)
+    out_ids, out_scores = [], []
+    for a in range(0, q.size, step):
+        b = min(a + step, q.size)
+        ids = torch.empty(b - a, k, dtype=torch.int32, device=dev)
+        scores = torch.empty(b - a, k, dtype=torch.float32, device=dev)
+        L.topk_similar(emb, inv, q32[a:b], cand, min_sim, k, ids, scores)
+        out_ids.append(ids.long())
+        out_scores.append(scores)
+    return torch.cat(out_ids), torch.cat(out_scores)
+
+
+def write_similar_items(item_embeddings, k, batch_size, item_names, path, item_ids=None, candidates=None, metric='cos', min_sim=None, Log_file=None):
+    """The runners' --mode similar: similar_items for the query items ``item_ids`` (default: every item 1 .. N), sharded over the data-parallel
+    ranks as write_recommendations shards its users.  Rank 0 writes ``path``: one line per query item, in query order,
+    ``item_name \\t name_1 ... name_k \\t score_1 ... score_k`` with the item file's names (pad slots omitted, scores as %.9g); an item without
+    any neighbour gets no line.  ``Log_file`` gets one line, ``similar``: the number of query items, how many have a neighbour, and their mean
+    best score.  Returns the path on rank 0, None elsewhere."""
+    n1 = item_embeddings.shape[0]
+    q = np.arange(1, n1, dtype=np.int64) if item_ids is None else np.asarray(item_ids, dtype=np.int64).reshape(-1)
+    nq = int(q.size)
+    if nq == 0:
+        raise ValueError('write_similar_items: no query item')
+    world, rank_id, rows = _shard_users(nq, batch_size)
+    ids, scores = similar_items(item_embeddings, k, q[np.asarray(rows, dtype=np.int64)], candidates, metric, min_sim)
+    ids, scores = _gather_cat(ids, world), _gather_cat(scores, world)
+    if rank_id != 0:
+        return None
+    ids, scores = ids[:nq].cpu().numpy(), scores[:nq].cpu().numpy()
+    has = ids[:, 0] != 0
+    with open(path, 'w') as f:
+        for r in range(nq):
+            if not has[r]:
+                continue
+            keep = ids[r] != 0
+            f.write(item_names[int(q[r])] + '\t' + ' '.join(item_names[int(i)] for i in ids[r][keep]) + '\t'
+                    + ' '.join('%.9g' % float(s) for s in scores[r][keep]) + '\n')
+    if Log_file is not None:
+        best = float(scores[has, 0].astype(np.float64).mean()) if has.any() else 0.0
+        Log_file.info('similar   top-{} lists of {} items, {} with a neighbour, mean best score {:0.5f} -> {}'.format(k, nq, int(has.sum()), best, path))
+    return path

@@ -18,7 +18,7 @@ from torch.utils.data import DataLoader
 
 from .data_utils import (BuildTrainDataset, eval_model, get_doc_input_bert, get_item_embeddings, read_behaviors,
                          read_news_bert)
-from .data_utils.eval_flags import check_flags, eval_restriction, write_recommend_mode
+from .data_utils.eval_flags import check_flags, eval_restriction, write_recommend_mode, write_similar_mode
 from .data_utils.dataset import DeviceTrainSampler
 from .data_utils.utils import (get_checkpoint, para_and_log, report_time_eval, report_time_train, save_model, setuplogger)
 from .ddp import FlatDDP, any_rank
@@ -206,7 +206,8 @@ def test(args, use_modal, local_rank, Log_file, Log_screen, model_dir, start_tim
 
 def recommend(args, use_modal, local_rank, Log_file, Log_screen, model_dir, start_time):
     """--mode recommend: the model test() evaluates, asked for the --topk next items after every kept user's whole known sequence (the test
-    split's input with its held-out item), everything in that sequence excluded; rank 0 writes --recommend_out."""
+    split's input with its held-out item), everything in that sequence excluded; rank 0 writes --recommend_out.
+    --mode similar: the same checkpoint and item table, asked for every item's --topk nearest items instead; rank 0 writes --similar_out."""
     tokenizer, bert_model = load_backbone(args, Log_file)
     path = os.path.join(args.root_data_dir, args.dataset, args.behaviors)
     before_id2dic, before_name2id = read_news_bert(os.path.join(args.root_data_dir, args.dataset, args.news), args, tokenizer)
@@ -215,6 +216,9 @@ def recommend(args, use_modal, local_rank, Log_file, Log_screen, model_dir, star
     model, _, _ = build_model(args, item_num, use_modal, bert_model, local_rank, Log_file, model_dir)
     model = FlatDDP(model, device_ids=[local_rank], output_device=local_rank)
     emb = get_item_embeddings(model, item_content, 512, args, use_modal, local_rank)
+    if args.mode == 'similar':                                         # the same table, asked for every item's nearest items: no user is encoded
+        write_similar_mode(args, emb, 512, path, before_name2id, model_dir, Log_file)
+        return
     write_recommend_mode(args, model, users_test, hist_test, emb, 512, path, before_name2id, model_dir, Log_file)
 
 
@@ -242,7 +246,7 @@ def main(argv=None):
     Log_file.info(args)
     os.makedirs(model_dir, exist_ok=True)
     t0 = time.time()
-    if args.mode == 'recommend':
+    if args.mode in ('recommend', 'similar'):
         recommend(args, use_modal, local_rank, Log_file, Log_screen, model_dir, t0)
     else:
         (test if 'test' in args.mode else train)(args, use_modal, local_rank, Log_file, Log_screen, model_dir, t0)

@@ -544,6 +544,7 @@ int a4r_score_ce_bwd_items(void* stream, const float* prec, const float* table, 
  * drawn items in one launch): a header of their own for the same reason, bound by adapter4rec_amd/_lib_eval_negatives.py. */
 #include "a4r_eval_negatives.h"
 #include "a4r_diversify.h"
+#include "a4r_similar.h"
 
 /* The learned item-ID table of the IDRec baseline (ABI 410; Downstream/CV/model/model.py: nn.Embedding(item_num + 1, E, padding_idx=0), fed the flat
  * slot ids of a batch).  a4r_id_index, once per step: rows[i] = ids[i] when 0 <= ids[i] <= item_num, else 0 and counted in *err (overwritten: the

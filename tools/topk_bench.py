@@ -2,7 +2,7 @@
 """Top-K recommendation on one MI355X: a4r_topk_items beside a4r_eval_rank (the same scoring sweep, one rank per user) and beside the torch path a
 user would otherwise write (chunked fp32 matmul, history masked, torch.topk), and recommend() end to end -- one JSON line per configuration.
 
-    python tools/topk_bench.py [--iters N] [--only NAME] [--candidates FRACTION] [--lists C] [--mmr]
+    python tools/topk_bench.py [--iters N] [--only NAME] [--candidates FRACTION] [--lists C] [--mmr] [--similar]
 
 --candidates FRACTION runs the candidate-set leg instead (cand_cfg): a4r_topk_items_cand / a4r_eval_rank_cand beside the unmasked entries, interleaved.
 --lists C runs the per-user-list leg instead (lists_cfg): a4r_topk_lists over C listed items per user (C = 0: 100, 1000 and 4096 in turn), E = 64 and
@@ -10,6 +10,9 @@ user would otherwise write (chunked fp32 matmul, history masked, torch.topk), an
 a4r_topk_items over the whole table for scale.
 --mmr runs the re-ranking leg instead (mmr_cfg): a4r_mmr_rerank cutting a4r_topk_items' pools of 100 and 256 items to 10, E = 64 and 128, lambda 0.7,
 beside the eager composition on the same pools (gather, bmm cosine matrix, a K-round loop from the host), interleaved.
+--similar runs the similar-items leg instead (similar_cfg): a4r_topk_similar (cosine) for 32 768 query items of a 65 537-row table, K = 10 and 100,
+E = 64 and 128, beside the composition of existing entries (normalised copy + gather + a4r_topk_items with one-id exclusion lists) and beside eager
+torch (normalise, chunked matmul, topk), interleaved rounds after a warm-up.
 
 Shapes: 32 768 users x 65 537 items (the evaluation benchmark's shape) and x 500 001 items (the ID tower's 500 000-item table), E = 64, K 10 / 100,
 histories of 20 uniform ids.  Kernel times are HIP-event means over N launches after a warm-up; per-kernel times: run this under
@@ -209,6 +212,64 @@ def mmr_cfg(name, U, N1, E, k, P, lam, iters, rounds=2, H=20):
                 lists_equal_to_eager=round(agree, 6), lists_changed_by_mmr=round(changed, 4))
 
 
+def eager_similar(emb, query, k, chunk=2048):
+    """what a caller without the kernel writes: a normalised copy, [chunk, N1] cosines, the pad row and the query itself masked, torch.topk"""
+    n = emb / emb.norm(dim=1, keepdim=True).clamp_min(1e-30)
+    ids, scores = [], []
+    for a in range(0, query.numel(), chunk):
+        q = query[a:a + chunk].long()
+        s = n[q] @ n.t()
+        s[:, 0] = -float('inf')
+        s.scatter_(1, q[:, None], -float('inf'))
+        v, i = torch.topk(s, k, dim=1)
+        ids.append(i)
+        scores.append(v)
+    return torch.cat(ids), torch.cat(scores)
+
+
+def similar_cfg(name, Q, N1, E, k, iters, rounds=3):
+    """--similar: the fused entry (inverse norms + a4r_topk_similar), its top-K launch alone, the composition (normalised copy, gather of the query
+    rows, a4r_topk_items with one-id exclusion lists; its a4r_topk_items launch alone as well) and eager torch, interleaved `rounds` times after a
+    warm-up; every round's mean is reported, the ratios from the minima, and the spread of each leg over its rounds."""
+    from adapter4rec_amd import _lib as L
+    g = torch.Generator(device=DEV).manual_seed(3)
+    emb = torch.randn(N1, E, device=DEV, generator=g)
+    query = (torch.randperm(N1 - 1, device=DEV, generator=g)[:Q] + 1).to(torch.int32).contiguous()
+    ids = torch.empty(Q, k, dtype=torch.int32, device=DEV)
+    sc = torch.empty(Q, k, dtype=torch.float32, device=DEV)
+    ids_c, sc_c = torch.empty_like(ids), torch.empty_like(sc)
+    ptr = torch.arange(Q + 1, device=DEV, dtype=torch.int32)
+    inv = L.row_inv_norms(emb)
+    normed = (emb * inv[:, None]).contiguous()
+    prec = normed[query.long()].contiguous()
+
+    def fused():
+        L.topk_similar(emb, L.row_inv_norms(emb), query, None, None, k, ids, sc)
+
+    def composition():
+        n = (emb / emb.norm(dim=1, keepdim=True).clamp_min(1e-30)).contiguous()
+        L.topk_items(n[query.long()].contiguous(), n, ptr, query, k, ids_c, sc_c)
+    legs = dict(similar=fused, similar_topk_only=lambda: L.topk_similar(emb, inv, query, None, None, k, ids, sc), composition=composition,
+                composition_topk_only=lambda: L.topk_items(prec, normed, ptr, query, k, ids_c, sc_c), eager=lambda: eager_similar(emb, query, k))
+    for fn in legs.values():                                        # warm-up: every leg once before any is timed
+        fn()
+    ms = {n: [] for n in legs}
+    for _ in range(rounds):
+        for n, fn in legs.items():
+            ms[n].append(round(timed(fn, iters if n != 'eager' else max(1, iters // 4)), 4))
+    fused()
+    composition()
+    ei, _ = eager_similar(emb, query, k)
+    spread = {n: round((max(v) - min(v)) / min(v), 4) for n, v in ms.items()}
+    best = min(ms['similar'])
+    return dict(name=name, queries=Q, items=N1, E=E, k=k, rounds=rounds, iters=iters, **{n + '_ms': v for n, v in ms.items()}, spread=spread,
+                similar_over_composition=round(best / min(ms['composition']), 3),
+                similar_topk_over_composition_topk=round(min(ms['similar_topk_only']) / min(ms['composition_topk_only']), 3),
+                eager_over_similar=round(min(ms['eager']) / best, 2), queries_per_s=round(Q / best * 1e3),
+                extra_table_bytes_of_the_composition=N1 * E * 4, id_agreement_with_composition=round(float((ids == ids_c).float().mean()), 6),
+                id_agreement_with_eager=round(float((ei.int() == ids).float().mean()), 6))
+
+
 def recommend_cfg(name, U, item_num, k, iters, T=20):
     from adapter4rec_amd.cv import Model
     from adapter4rec_amd.cv.data_utils import get_itemId_embeddings
@@ -239,7 +300,16 @@ def main():
                     help="run the per-user-list leg instead: a4r_topk_lists over C listed items per user beside the eager gather path (0: every C)")
     ap.add_argument('--mmr', action='store_true',
                     help='run the re-ranking leg instead: a4r_mmr_rerank beside the eager gather + bmm + K-round loop, pools of 100 and 256, E = 64 and 128')
+    ap.add_argument('--similar', action='store_true',
+                    help='run the similar-items leg instead: a4r_topk_similar beside the composition of existing entries and eager torch, K = 10 and 100, E = 64 and 128')
     a = ap.parse_args()
+    if a.similar:
+        for k in (10, 100):
+            for E in (64, 128):
+                name = f'similar_k{k}_e{E}'
+                if not a.only or a.only == name:
+                    print(json.dumps(similar_cfg(name, 32768, 65537, E, k, a.iters)), flush=True)
+        return
     if a.mmr:
         for P in (100, 256):
             for E in (64, 128):
