@@ -150,6 +150,122 @@ __global__ void __launch_bounds__(256) topk_partial_kernel(const float* __restri
     }
 }
 
+// Scores from the bf16 MFMA (a4r_topk_items_bf16, include/a4r_score_bf16.h): topk_partial_kernel at prec_b = bf16(prec), table_b = bf16(item_emb),
+// the scores by eval_rank_bf16_kernel's chain (score_tile<bf16_t>), so the two entries give the same bits.  A workgroup holds RS sets of 16 users:
+// the A fragments, the buffer, the threshold, counter and exclusion arrays are 16 RS users wide, a table tile is loaded once for all of them, and
+// PD tiles are in flight per wave (the ring of eval_rank_bf16_kernel).  A step still adds at most STEP_KEYS keys per USER, so cap, the trigger and
+// topk_compact -- called once per row set on that set's 16 buffers -- are as above; so are the key, the merge and the decode.
+template <int E, int RS, int PD, bool CAND>
+__global__ void __launch_bounds__(256) topk_partial_bf16_kernel(const bf16_t* __restrict__ prec, const bf16_t* __restrict__ table,
+                                                                const int32_t* __restrict__ excl_ptr, const int32_t* __restrict__ excl_idx,
+                                                                uint64_t* __restrict__ ws, int U, int N1, int K, int cap,
+                                                                const uint8_t* __restrict__ cand) {
+    constexpr int KS = E / 32;                       // chunk steps (bf16: 32 k per step)
+    constexpr int PER = (MAXX + 15) / 16;            // exclusion ids per thread while sorting
+    constexpr int R = 16 * RS;                       // users of a workgroup
+    extern __shared__ uint64_t buf[];                // [R][cap] candidate keys
+    __shared__ int32_t excl[R][MAXX];
+    __shared__ int32_t nex[R];
+    __shared__ int32_t cnt[R];
+    __shared__ uint64_t thr_s[R];
+    __shared__ int trig;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int r16 = lane & 15, kg = lane >> 4;
+    const int u0 = blockIdx.x * R;
+    if (tid == 0) trig = -1;
+    for (int rs = 0; rs < RS; ++rs) {   // 16 threads per user copy its exclusion ids and put them in ascending order, one row set at a time (the sets' rows are disjoint)
+        const int ul = rs * 16 + (tid >> 4), j0 = tid & 15, u = min(u0 + ul, U - 1);
+        const int b = excl_ptr[u], n = max(0, min(excl_ptr[u + 1] - b, MAXX));
+        for (int j = j0; j < n; j += 16) excl[ul][j] = excl_idx[b + j];
+        if (j0 == 0) { nex[ul] = n; cnt[ul] = 0; thr_s[ul] = 0; }
+        __syncthreads();
+        int v[PER], pos[PER];
+#pragma unroll
+        for (int m = 0; m < PER; ++m) {
+            const int j = j0 + 16 * m;
+            pos[m] = -1; v[m] = 0;
+            if (j < n) {
+                const int x = excl[ul][j];
+                int p = 0;
+                for (int k = 0; k < n; ++k) {
+                    const int y = excl[ul][k];
+                    p += (y < x || (y == x && k < j)) ? 1 : 0;
+                }
+                v[m] = x; pos[m] = p;
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int m = 0; m < PER; ++m)
+            if (pos[m] >= 0) excl[ul][pos[m]] = v[m];
+    }
+    uint4 ua[RS][KS];                                // A operand: RS sets of 16 users
+#pragma unroll
+    for (int rs = 0; rs < RS; ++rs) frag_load<E>(ua[rs], prec, min(u0 + rs * 16 + r16, U - 1), kg);
+    __syncthreads();
+    const SweepDeal<> deal(N1, wave);
+    const int nsteps = deal.steps();                 // the 4 waves meet at every step's barrier
+    uint64_t thr[RS][4];
+    bool live[RS][4];
+#pragma unroll
+    for (int rs = 0; rs < RS; ++rs)
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) { thr[rs][rr] = 0; live[rs][rr] = u0 + rs * 16 + kg * 4 + rr < U; }
+    uint4 bn[PD][KS];
+#pragma unroll
+    for (int j = 0; j < PD; ++j) frag_load<E>(bn[j], table, deal.row(deal.first + j * deal.tstep, r16), kg);
+    for (int sb = 0; sb < nsteps; sb += PD) {
+#pragma unroll
+        for (int j = 0; j < PD; ++j) {
+            const int s = sb + j;
+            if (s < nsteps) {                             // uniform over the workgroup
+                const int t = deal.first + s * deal.tstep;
+                const int i = 1 + t * 16 + r16;           // this lane's item column (>= N1 past the end of the table: nothing to add)
+                uint4 b[KS];
+#pragma unroll
+                for (int ks = 0; ks < KS; ++ks) b[ks] = bn[j][ks];
+                frag_load<E>(bn[j], table, deal.row(t + PD * deal.tstep, r16), kg);
+#pragma unroll
+                for (int rs = 0; rs < RS; ++rs) {
+                    const f32x4_t acc = score_tile<bf16_t>(ua[rs], b);
+#pragma unroll
+                    for (int rr = 0; rr < 4; ++rr) {
+                        const uint64_t key = topk_key(acc[rr], i);
+                        if (i < N1 && live[rs][rr] && key > thr[rs][rr]) {
+                            if constexpr (CAND)
+                                if (cand[i] == 0) continue;
+                            const int ul = rs * 16 + kg * 4 + rr;
+                            int lo = 0, hi = nex[ul];
+                            while (lo < hi) {
+                                const int mid = (lo + hi) >> 1;
+                                if (excl[ul][mid] < i) lo = mid + 1; else hi = mid;
+                            }
+                            if (!(lo < nex[ul] && excl[ul][lo] == i)) {
+                                const int p = atomicAdd(&cnt[ul], 1);
+                                buf[(size_t)ul * cap + p] = key;
+                                if (p >= cap - STEP_KEYS) trig = s;      // (as in topk_partial_kernel)
+                            }
+                        }
+                    }
+                }
+                __syncthreads();
+                if (trig == s) {                          // uniform, as in topk_partial_kernel
+                    for (int rs = 0; rs < RS; ++rs) topk_compact(buf + (size_t)rs * 16 * cap, cap, K, cnt + rs * 16, thr_s + rs * 16);
+#pragma unroll
+                    for (int rs = 0; rs < RS; ++rs)
+#pragma unroll
+                        for (int rr = 0; rr < 4; ++rr) thr[rs][rr] = thr_s[rs * 16 + kg * 4 + rr];
+                }
+            }
+        }
+    }
+    for (int rs = 0; rs < RS; ++rs) topk_compact(buf + (size_t)rs * 16 * cap, cap, K, cnt + rs * 16, thr_s + rs * 16);
+    for (int e = tid; e < R * K; e += 256) {
+        const int ul = e / K, j = e - ul * K;
+        if (u0 + ul < U) ws[((size_t)blockIdx.y * U + u0 + ul) * K + j] = buf[(size_t)ul * cap + j];
+    }
+}
+
 // Similar items (a4r_topk_similar, include/a4r_similar.h): topk_partial_kernel with the 16 rows of a workgroup taken from the table itself.  The A
 // fragments are loaded straight from item_emb[query[..]] (no gather); one compare i == q stands where the exclusion list, its LDS and its sorting
 // prologue were.  COS is the cosine metric (inv non-null): score = dot * (inv[q] * inv[i]); inv[i] of the lane's item column is requested with that
@@ -327,6 +443,55 @@ int topk_launch(void* stream, const float* prec, const float* item_emb, const in
     return a4r_launch_status();
 }
 
+// Row sets of a4r_topk_items_bf16 per (E, K).  LDS bounds them: a row set is a 16-user buffer of 16 cap keys (16 / 32 / 64 KB at K <= 64 / <= 192 / <= 256)
+// beside 17 KB of exclusion ids, so two sets at K <= 64 are 66 KB (two workgroups a CU) and two sets above are one workgroup a CU or none.  Timings
+// choose within that: two sets at E = 128 / 256, where the table's bytes bind; one at E = 64, where the second set's LDS halves
+// the workgroups a CU holds and the launch ran twice as long; one at E = 512, where the A fragments of two sets are 128 VGPRs beside the tiles.
+int topk_bf16_rs(int E, int K) { return (K <= 64 && (E == 128 || E == 256)) ? 2 : 1; }
+template <int E> struct TopkBf16Shape { static constexpr int PD = E == 64 ? 4 : E == 128 ? 2 : 1; };      // tiles in flight per wave
+
+int topk_bf16_ranges(int U, int N1, int rs) {        // sweep_ranges over workgroups of 16 rs users, at most MAX_RANGES item ranges
+    const int gy = sweep_ranges((U + rs - 1) / rs, N1);
+    return gy < MAX_RANGES ? gy : MAX_RANGES;
+}
+
+template <int E, int RS, bool CAND>
+int topk_bf16_partial(hipStream_t s, const bf16_t* prec, const bf16_t* table, const int32_t* excl_ptr, const int32_t* excl_idx, const uint8_t* cand,
+                      uint64_t* w, int U, int N1, int K, int gy) {
+    const int cap = topk_cap(K);
+    const dim3 grid((U + 16 * RS - 1) / (16 * RS), gy);
+    const size_t lds = (size_t)16 * RS * cap * sizeof(uint64_t);
+    const auto kernel = topk_partial_bf16_kernel<E, RS, TopkBf16Shape<E>::PD, CAND>;
+    if (int rc = a4r_set_lds(kernel, lds)) return rc;
+    hipLaunchKernelGGL(kernel, grid, dim3(256), lds, s, prec, table, excl_ptr, excl_idx, w, U, N1, K, cap, cand);
+    return A4R_OK;
+}
+
+template <bool CAND>
+int topk_bf16_launch(hipStream_t s, const bf16_t* prec, const bf16_t* table, const int32_t* excl_ptr, const int32_t* excl_idx, const uint8_t* cand,
+                     int32_t* ids, float* scores, uint64_t* w, int U, int N1, int E, int K) {
+    const int rs = topk_bf16_rs(E, K), gy = topk_bf16_ranges(U, N1, rs);
+    int rc = A4R_OK;
+    with_width(WidthsF32{}, E, [&](auto e) {
+        constexpr int W = decltype(e)::value;
+        if constexpr (W == 128 || W == 256) {
+            if (rs == 2) { rc = topk_bf16_partial<W, 2, CAND>(s, prec, table, excl_ptr, excl_idx, cand, w, U, N1, K, gy); return; }
+        }
+        rc = topk_bf16_partial<W, 1, CAND>(s, prec, table, excl_ptr, excl_idx, cand, w, U, N1, K, gy);
+    });
+    if (rc) return rc;
+    if (gy == 1) {
+        const int64_t n = (int64_t)U * K;
+        const int blocks = (int)((n + 255) / 256 < 8192 ? (n + 255) / 256 : 8192);
+        hipLaunchKernelGGL(topk_decode_kernel, dim3(blocks), dim3(256), 0, s, w, ids, scores, n);
+    } else {
+        const size_t mlds = (size_t)gy * K * sizeof(uint64_t);
+        if ((rc = a4r_set_lds(topk_merge_kernel, mlds))) return rc;
+        hipLaunchKernelGGL(topk_merge_kernel, dim3(U), dim3(256), mlds, s, w, ids, scores, U, K, gy);
+    }
+    return a4r_launch_status();
+}
+
 // a4r_topk_similar's launches: the partial kernel above over top-K's grid with U = Q, then top-K's own decode or merge
 template <bool CAND, bool COS>
 int similar_launch(hipStream_t s, const float* item_emb, const float* inv, const int32_t* query, const uint8_t* cand, float min_sim, int32_t* ids,
@@ -379,6 +544,24 @@ extern "C" int a4r_topk_similar(void* stream, const float* item_emb, const float
 extern "C" size_t a4r_topk_ws_bytes(int U, int N1, int K) {
     if (!topk_shape_ok(U, N1, K)) return 0;
     return (size_t)topk_ranges(U, N1) * (size_t)U * (size_t)K * sizeof(uint64_t);
+}
+
+extern "C" size_t a4r_topk_bf16_ws_bytes(int U, int N1, int E, int K) {
+    if (!topk_shape_ok(U, N1, K) || !width_served(WidthsF32{}, E)) return 0;
+    return (size_t)topk_bf16_ranges(U, N1, topk_bf16_rs(E, K)) * (size_t)U * (size_t)K * sizeof(uint64_t);
+}
+
+extern "C" int a4r_topk_items_bf16(void* stream, const void* prec_b, const void* table_b, const int32_t* excl_ptr, const int32_t* excl_idx,
+                                   const uint8_t* cand, int32_t* ids, float* scores, void* ws, int U, int N1, int E, int K) {
+    if (!prec_b || !table_b || !excl_ptr || !excl_idx || !ids || !scores || !ws || !topk_shape_ok(U, N1, K)) return A4R_EINVAL;
+    if (!width_served(WidthsF32{}, E) || !aligned16(prec_b, table_b)) return A4R_EINVAL;
+    if (reinterpret_cast<uintptr_t>(ws) & 7u) return A4R_EINVAL;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const bf16_t* prec = static_cast<const bf16_t*>(prec_b);
+    const bf16_t* table = static_cast<const bf16_t*>(table_b);
+    uint64_t* w = static_cast<uint64_t*>(ws);
+    return cand ? topk_bf16_launch<true>(s, prec, table, excl_ptr, excl_idx, cand, ids, scores, w, U, N1, E, K)
+                : topk_bf16_launch<false>(s, prec, table, excl_ptr, excl_idx, nullptr, ids, scores, w, U, N1, E, K);
 }
 
 extern "C" int a4r_topk_items(void* stream, const float* prec, const float* item_emb, const int32_t* excl_ptr, const int32_t* excl_idx,

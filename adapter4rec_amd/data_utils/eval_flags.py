@@ -8,7 +8,7 @@ import torch.distributed as dist
 
 from .._lib_diversify import MMR_MAX_POOL
 from .._lib_user_lists import LIST_MAX
-from .metrics import (SIMILAR_METRICS, Diversify, EvalNegatives, candidate_mask, item_counts, read_candidate_lists, read_candidates,
+from .metrics import (SCORE_DTYPES, SIMILAR_METRICS, Diversify, EvalNegatives, candidate_mask, item_counts, read_candidate_lists, read_candidates,
                       read_similar_items, write_eval_negatives, write_recommendations, write_similar_items)
 from .preprocess import read_behavior_names
 
@@ -29,6 +29,7 @@ def add_eval_flags(p):
     p.add_argument('--similar_items', type=str, default=None)          # --mode similar: a file of item names, one per line -- the query items, in file order (default: every item)
     p.add_argument('--similar_metric', type=str, default='cos', choices=list(SIMILAR_METRICS))      # --mode similar: cosine, or the dot product --mode recommend ranks by
     p.add_argument('--similar_min', type=float, default=None)          # --mode similar: list only the items scoring at least this (0.95 under cos: near-duplicates)
+    p.add_argument('--score_dtype', type=str, default='fp32', choices=list(SCORE_DTYPES))      # --mode test / recommend and the per-epoch evaluation: bf16 = score against the item table on the bf16 MFMA (operands rounded, fp32 sums)
 
 
 def check_flags(args):
@@ -37,6 +38,32 @@ def check_flags(args):
     check_eval_negatives_flag(args)
     check_diversify_flag(args)
     check_similar_flag(args)
+    check_score_dtype_flag(args)
+
+
+def check_score_dtype_flag(args):
+    """--score_dtype bf16 is honoured by --mode test, the per-epoch evaluation of --mode train and --mode recommend, alone or beside
+    --candidate_items; beside --candidate_lists, --eval_negatives, --diversify mmr and under --mode similar it is refused instead of ignored:
+    their kernels score in fp32 only.  --ce_dtype is independent of it."""
+    if getattr(args, 'score_dtype', 'fp32') == 'fp32':
+        return
+    if args.mode == 'similar':
+        raise ValueError('--score_dtype bf16 is not honoured by --mode similar: a4r_topk_similar scores in fp32 only')
+    if getattr(args, 'candidate_lists', None):
+        raise ValueError('--score_dtype bf16 and --candidate_lists cannot be combined: the kernels of a user\'s own list score in fp32 only')
+    if int(getattr(args, 'eval_negatives', 0) or 0) != 0:
+        raise ValueError('--score_dtype bf16 and --eval_negatives cannot be combined: the sampled evaluation scores in fp32 only')
+    if getattr(args, 'diversify', 'none') != 'none':
+        raise ValueError(f'--score_dtype bf16 and --diversify {args.diversify} cannot be combined: the re-ranking scores in fp32 only')
+
+
+def score_dtype_from_args(args, Log_file):
+    """--score_dtype as the ``score_dtype`` keyword of eval_model / write_recommendations: {} under the default (the calls are then the ones made
+    before), else the keyword, and one log line naming the dtype."""
+    if getattr(args, 'score_dtype', 'fp32') == 'fp32':
+        return {}
+    Log_file.info(f'score dtype: {args.score_dtype} (item-table scores on the bf16 MFMA: operands rounded to nearest even, fp32 sums)')
+    return dict(score_dtype=args.score_dtype)
 
 
 def check_similar_flag(args):
@@ -136,7 +163,8 @@ def eval_negatives_from_args(args, users_train, item_num, Log_file):
 def eval_restriction(args, behaviors_path, name2id, users_train, hist_test, users_test, item_num, dev, Log_file):
     """The flags as eval_model's restriction keywords, for every evaluation of a run: {} without a flag (the calls are then the ones made
     before), else one of ``candidates`` (--candidate_items: the mask uploaded to ``dev`` here, once for both splits), ``candidate_lists``
-    (--candidate_lists) and ``eval_negatives`` (--eval_negatives; with --eval_negatives_out, rank 0 writes the test split's draws).  check_flags
+    (--candidate_lists) and ``eval_negatives`` (--eval_negatives; with --eval_negatives_out, rank 0 writes the test split's draws), and beside
+    none or ``candidates``, ``score_dtype`` (--score_dtype bf16).  check_flags
     has refused every pair of them, and the candidate flags outside --mode test.  The behaviours file is read for its names at most once."""
     out = getattr(args, 'eval_negatives_out', None) and dist.get_rank() == 0
     user_names = item_names = None
@@ -152,6 +180,7 @@ def eval_restriction(args, behaviors_path, name2id, users_train, hist_test, user
         if out:
             k = write_eval_negatives(neg, hist_test, users_test, item_num + 1, args, user_names, item_names, args.eval_negatives_out, dev)
             Log_file.info(f'eval negatives: the draws of the test split for {k} users -> {args.eval_negatives_out}')
+    kw.update(score_dtype_from_args(args, Log_file))
     return kw
 
 
@@ -170,7 +199,8 @@ def write_recommend_mode(args, model, users_test, hist_test, item_embeddings, ba
         spec = Diversify(args.mmr_lambda, args.mmr_pool)
         Log_file.info(f'diversify: mmr, lambda {spec.lam:g}, pool {spec.pool}')
     out = write_recommendations(model, users_test, hist_test, item_embeddings, args.topk, batch_size, args, user_names, item_names,
-                                recommend_out_path(args, model_dir), candidates=mask, candidate_lists=lists, diversify=spec, Log_file=Log_file)
+                                recommend_out_path(args, model_dir), candidates=mask, candidate_lists=lists, diversify=spec, Log_file=Log_file,
+                                **score_dtype_from_args(args, Log_file))
     if out:
         Log_file.info(f'recommend: top-{args.topk} lists of {len(users_test)} users -> {out}')
 

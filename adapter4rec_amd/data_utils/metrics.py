@@ -253,6 +253,27 @@ def candidate_lists_csr(candidate_lists, uids):
     return _csr_int32(ls)
 
 
+SCORE_DTYPES = ('fp32', 'bf16')
+
+
+def _score_dtype_checked(score_dtype, **fp32_only):
+    """``score_dtype`` validated; under 'bf16' every given restriction whose kernels are fp32-only is refused, not ignored."""
+    if score_dtype not in SCORE_DTYPES:
+        raise ValueError(f'score_dtype {score_dtype!r}, expected one of {SCORE_DTYPES}')
+    if score_dtype == 'bf16':
+        for name, value in fp32_only.items():
+            if value is not None:
+                raise ValueError(f"score_dtype 'bf16' cannot be combined with {name}: its kernels score in fp32 only")
+    return score_dtype
+
+
+def _cast_bf16(x):
+    """The bf16 copy (round to nearest even, a4r_score_ce_bf16_cast) of a contiguous fp32 device tensor"""
+    out = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device)
+    L.cast_bf16(x, out)
+    return out
+
+
 def _both_refused(candidates, candidate_lists, eval_negatives=None):
     if candidates is not None and candidate_lists is not None:
         raise ValueError('candidates (one set for all users) and candidate_lists (a list per user) cannot be combined: give one of them')
@@ -390,7 +411,7 @@ def write_eval_negatives(spec, user_history, eval_seq, n1, args, user_names, ite
 
 
 def eval_ranks(model, user_history, eval_seq, item_embeddings, test_batch_size, args, user_ids, candidates=None, candidate_lists=None,
-               eval_negatives=None):
+               eval_negatives=None, score_dtype='fp32'):
     """Rank (1 = best) of each listed user's held-out target among all items not in the user's history.  ``candidates`` (candidate_mask's
     input): among the candidate items only -- for every listed user; a target that is no candidate gets the rank it would have if it were.
     ``candidate_lists`` (a mapping, or a sequence indexed by user id, from user to an iterable of item ids, at most LIST_MAX each): among the
@@ -398,8 +419,12 @@ def eval_ranks(model, user_history, eval_seq, item_embeddings, test_batch_size, 
     not be listed.  ``eval_negatives`` (an EvalNegatives): among the negatives drawn for the user on the device (a4r_eval_rank_sampled: one
     launch per batch draws, scores and ranks; the user's key is its id here, so the draws do not depend on the batch, the shard or the epoch); a
     user without a candidate gets rank 1 and is counted in ``eval_negatives.last_err``, a pinned word filled by an asynchronous copy: read it
-    after the next synchronisation."""
+    after the next synchronisation.  ``score_dtype`` 'bf16': the scores come from the bf16 MFMA at the rounded operands
+    (a4r_eval_rank_bf16; the rule is in include/a4r_score_bf16.h) -- the table is cast once per call and each batch's user vectors once; the user
+    tower still reads its input rows from the fp32 table, so the user vectors are the ones of 'fp32'.  Honoured with and without ``candidates``;
+    refused beside ``candidate_lists`` and ``eval_negatives``, whose kernels score in fp32 only."""
     _both_refused(candidates, candidate_lists, eval_negatives)
+    bf16 = _score_dtype_checked(score_dtype, candidate_lists=candidate_lists, eval_negatives=eval_negatives) == 'bf16'
     inner = _inner(model, args)
     dev = next(model.parameters()).device
     emb = item_embeddings.to(dev).float().contiguous()
@@ -409,6 +434,7 @@ def eval_ranks(model, user_history, eval_seq, item_embeddings, test_batch_size, 
     if len(user_ids) == 0:
         return torch.zeros(0, dtype=torch.int32, device=dev)
     P = _prepare_eval_set(eval_seq, user_history, Lm, dev)
+    emb_b = _cast_bf16(emb) if bf16 else None                     # the scoring copy; the fp32 table stays: the user tower reads it
     uid_all = np.asarray(user_ids, dtype=np.int64)
     # (the sampler pads its tail by REPEATING the last user: a repeated id takes the rank of the entry before it)
     first = np.concatenate([[True], np.diff(uid_all) != 0])
@@ -437,7 +463,9 @@ def eval_ranks(model, user_history, eval_seq, item_embeddings, test_batch_size, 
                 prec = inner.user_encoder(input_embs, P['mask'][a:b], None)[:, -1].contiguous()
                 ptr, hist, target = _batch_slices(P, a, b)
                 rank = torch.zeros(nb, dtype=torch.int32, device=dev)
-                if eval_negatives is not None:
+                if bf16:
+                    L.eval_rank_bf16(_cast_bf16(prec), emb_b, target, ptr, hist, rank, cand)
+                elif eval_negatives is not None:
                     L.eval_rank_sampled(prec, emb, target, ptr, hist, torch.arange(a, b, dtype=torch.int32, device=dev), neg_cdf,
                                         eval_negatives.seed, eval_negatives.n, rank, neg_err)
                 elif candidate_lists is not None:
@@ -460,14 +488,15 @@ def eval_ranks(model, user_history, eval_seq, item_embeddings, test_batch_size, 
 
 
 def eval_model(model, user_history, eval_seq, item_embeddings, test_batch_size, args, item_num, Log_file, v_or_t, local_rank, candidates=None,
-               candidate_lists=None, eval_negatives=None):
+               candidate_lists=None, eval_negatives=None, score_dtype='fp32'):
     """metrics.py:82-116.  Returns mean Hit@10 over all users (ranks are gathered over the data-parallel group).  ``candidates``
     (candidate_mask's input): every target is ranked among the candidate items only, and the means run over the users whose target is a
     candidate (cold-start and split evaluation); ValueError when there is no such user.  ``candidate_lists`` (eval_ranks'): every target is
     ranked among the user's own listed items, and the means run over the users who have a list; ValueError when no user has one.
     ``eval_negatives`` (an EvalNegatives): every target is ranked among the negatives drawn for its user on the device -- the sampled protocol of
-    the SASRec / IDRec papers -- and the means run over the users who had an item left to draw."""
+    the SASRec / IDRec papers -- and the means run over the users who had an item left to draw.  ``score_dtype``: eval_ranks'."""
     _both_refused(candidates, candidate_lists, eval_negatives)
+    _score_dtype_checked(score_dtype, candidate_lists=candidate_lists, eval_negatives=eval_negatives)
     n_users = len(eval_seq)
     world, _, user_ids = _shard_users(n_users, test_batch_size)
     model.eval()
@@ -476,7 +505,7 @@ def eval_model(model, user_history, eval_seq, item_embeddings, test_batch_size, 
     cand = candidate_mask(candidates, item_embeddings.shape[0], dev)          # uploaded once; eval_ranks takes it as it is
     Log_file.info(v_or_t + '_methods   {}'.format('\t'.join(['Hit{}'.format(topK), 'nDCG{}'.format(topK)])))
     ranks = eval_ranks(model, user_history, eval_seq, item_embeddings, test_batch_size, args, user_ids, candidates=cand,
-                       candidate_lists=candidate_lists, eval_negatives=eval_negatives).float()
+                       candidate_lists=candidate_lists, eval_negatives=eval_negatives, score_dtype=score_dtype).float()
     valid, label, what = _validity(user_history, eval_seq, item_embeddings.shape[0], args, user_ids, dev, cand, candidate_lists, eval_negatives)
     hr = _means_over_valid(ranks, valid, n_users, topK, world, Log_file, v_or_t, label, what)
     if eval_negatives is not None and eval_negatives.last_err is not None:
@@ -545,7 +574,8 @@ def _recommend_inputs(user_seqs, exclude, uids, T):
     return ids, mask, ptr, flat
 
 
-def recommend(model, user_seqs, item_embeddings, k, args, exclude=None, user_ids=None, candidates=None, candidate_lists=None, diversify=None):
+def recommend(model, user_seqs, item_embeddings, k, args, exclude=None, user_ids=None, candidates=None, candidate_lists=None, diversify=None,
+              score_dtype='fp32'):
     """The k best items for each listed user (default: every user of ``user_seqs``), after the user's sequence.
 
     ``user_seqs[u]``: the user's item ids (1 .. N); its last ``max_seq_len`` items go through ``user_encoder``, left-padded as an evaluation
@@ -560,14 +590,18 @@ def recommend(model, user_seqs, item_embeddings, k, args, exclude=None, user_ids
     the user's own listed items (a4r_topk_lists) -- a retrieval stage's shortlist, re-ranked; a user without a list gets pad slots only.
     ``diversify`` (a Diversify; k <= its pool): the entry above fills a pool of ``diversify.pool`` items per user instead, and a4r_mmr_rerank picks
     the k of them to return -- near-duplicates of an item already in the list give way to other items.  The scores are still the relevance
-    scores, in pick order: they need not descend."""
-    return _recommend(model, user_seqs, item_embeddings, k, args, exclude, user_ids, candidates, candidate_lists, diversify, False)[:2]
+    scores, in pick order: they need not descend.
+    ``score_dtype`` 'bf16': the scores come from the bf16 MFMA at the rounded operands (a4r_topk_items_bf16, include/a4r_score_bf16.h: the bits
+    eval_ranks(score_dtype='bf16') compares) -- the table is cast once per call, each batch's user vectors once; the returned scores are those
+    fp32 sums.  Honoured with and without ``candidates``; refused beside ``candidate_lists`` and ``diversify``, whose kernels score in fp32 only."""
+    return _recommend(model, user_seqs, item_embeddings, k, args, exclude, user_ids, candidates, candidate_lists, diversify, False, score_dtype)[:2]
 
 
-def _recommend(model, user_seqs, item_embeddings, k, args, exclude, user_ids, candidates, candidate_lists, diversify, want_ild):
+def _recommend(model, user_seqs, item_embeddings, k, args, exclude, user_ids, candidates, candidate_lists, diversify, want_ild, score_dtype='fp32'):
     """recommend's body -> (ids, scores, ild): ild None unless ``want_ild`` under ``diversify``, then fp32 [U, 2] = the intra-list diversity (mean
     1 - cosine over a list's pairs of items) of the plain top-k list and of the re-ranked one, both from the one pool."""
     _both_refused(candidates, candidate_lists)
+    bf16 = _score_dtype_checked(score_dtype, candidate_lists=candidate_lists, diversify=diversify) == 'bf16'
     if diversify is not None and not 1 <= int(k) <= diversify.pool:
         raise ValueError(f'diversify: k = {int(k)} outside 1 .. pool = {diversify.pool}')
     inner = _inner(model, args)
@@ -586,6 +620,7 @@ def _recommend(model, user_seqs, item_embeddings, k, args, exclude, user_ids, ca
     ids_np, mask_np, ptr_np, flat_np = _recommend_inputs(user_seqs, exclude, uids, T)
     step = int(os.environ.get('A4R_EVAL_USER_BATCH', 0)) or 8192          # (eval_ranks' user batch)
     flat = torch.from_numpy(flat_np).to(dev)
+    emb_b = _cast_bf16(emb) if bf16 else None                     # the scoring copy; the fp32 table stays: the user tower reads it
     if candidate_lists is not None:                               # the CSR of the users' own lists, uploaded once, sliced per batch
         lptr, lflat_np, llens = candidate_lists_csr(candidate_lists, uids)
         lflat = torch.from_numpy(lflat_np).to(dev)
@@ -602,7 +637,9 @@ def _recommend(model, user_seqs, item_embeddings, k, args, exclude, user_ids, ca
             ptr = torch.from_numpy((ptr_np[a:b + 1] - h0).astype(np.int32)).to(dev)
             ids = torch.empty(nb, kk, dtype=torch.int32, device=dev)
             scores = torch.empty(nb, kk, dtype=torch.float32, device=dev)
-            if candidate_lists is not None:
+            if bf16:
+                L.topk_items_bf16(_cast_bf16(prec), emb_b, ptr, flat[h0:h1 + 1], kk, ids, scores, cand)
+            elif candidate_lists is not None:
                 l0, l1 = int(lptr[a]), int(lptr[b])
                 L.topk_lists(prec, emb, torch.from_numpy((lptr[a:b + 1] - l0).astype(np.int32)).to(dev), lflat[l0:l1 + 1], int(llens[a:b].max()),
                              ptr, flat[h0:h1 + 1], kk, ids, scores)
@@ -626,7 +663,7 @@ def _recommend(model, user_seqs, item_embeddings, k, args, exclude, user_ids, ca
 
 
 def write_recommendations(model, user_seqs, user_history, item_embeddings, k, batch_size, args, user_names, item_names, path, candidates=None,
-                          candidate_lists=None, diversify=None, Log_file=None):
+                          candidate_lists=None, diversify=None, Log_file=None, score_dtype='fp32'):
     """The runners' --mode recommend: the k next items after every user's whole known sequence (``user_seqs[u]``, the evaluation input of the
     test split, whose last item is the held-out one), excluding ``user_history[u]`` plus that last item -- everything the user is known to have
     seen.  Users are sharded over the data-parallel ranks as eval_model shards them; rank 0 writes ``path``: one line per user, in uid order,
@@ -634,7 +671,8 @@ def write_recommendations(model, user_seqs, user_history, item_embeddings, k, ba
     ``candidates``, ``candidate_lists``: as recommend's; under ``candidate_lists`` a user without a list gets no line.
     ``diversify``: as recommend's.  The file's format is unchanged; a line's scores are the items' relevance scores in the order the items were
     picked, no longer necessarily descending.  ``Log_file`` then gets one line, ``recommend_ild``: the mean intra-list diversity (mean 1 - cosine
-    over a list's pairs of items) of the plain top-k lists and of the re-ranked ones, over the users with at least two items (``k of n users``)."""
+    over a list's pairs of items) of the plain top-k lists and of the re-ranked ones, over the users with at least two items (``k of n users``).
+    ``score_dtype``: as recommend's."""
     n_users = len(user_seqs)
     world, rank_id, uids = _shard_users(n_users, batch_size)
     exclude = {}
@@ -642,7 +680,7 @@ def write_recommendations(model, user_seqs, user_history, item_embeddings, k, ba
         u = int(u)
         if u not in exclude:
             exclude[u] = np.concatenate([np.asarray(user_history[u], dtype=np.int64).reshape(-1), np.asarray(user_seqs[u][-1:], dtype=np.int64)])
-    ids, scores, ild = _recommend(model, user_seqs, item_embeddings, k, args, exclude, uids, candidates, candidate_lists, diversify, True)
+    ids, scores, ild = _recommend(model, user_seqs, item_embeddings, k, args, exclude, uids, candidates, candidate_lists, diversify, True, score_dtype)
     ids, scores = _gather_cat(ids, world), _gather_cat(scores, world)
     if ild is not None:                                            # gathered over the ranks the way the ids are
         ild = _gather_cat(ild, world)

@@ -1,12 +1,14 @@
 #!/usr/bin/env python
 """Throughput of the native evaluation (reference: Downstream/Text/data_utils/metrics.py:62-116).
 
-  python tools/eval_bench.py [--items 65536] [--users 32768] [--json out.json] [--candidates FRACTION] [--sampled N [N ...]]
+  python tools/eval_bench.py [--items 65536] [--users 32768] [--json out.json] [--candidates FRACTION] [--sampled N [N ...]] [--bf16]
 
 --candidates FRACTION runs the candidate-set leg instead (candidates_leg): a4r_eval_rank_cand beside a4r_eval_rank, kernels only.
 --sampled N [N ...] runs the sampled-evaluation leg instead (sampled_leg): a4r_eval_rank_sampled beside the two-launch composition
 (a4r_eval_draw_negatives + a4r_eval_rank_lists), the full sweep a4r_eval_rank and an eager torch path, kernels only; one JSON line per
 configuration, appended to --json (the numbers land in profiles/eval_negatives_bench.jsonl).
+--bf16 runs the bf16-score leg instead (bf16_leg): a4r_eval_rank_bf16 beside the fp32 entries of the same build, kernels only, the casts in one
+leg and outside another; one JSON line per configuration, appended to --json (the numbers land in profiles/score_bf16_bench.jsonl).
 
 Times, on one MI355X, with BERT-base + Houlsby weights (random init, as bench.py):
   * the item sweep `get_item_embeddings` (all N + 1 titles through the item encoder, forward only) in the eval dtypes
@@ -149,6 +151,82 @@ def sampled_leg(a, dev):
                     out.flush()
 
 
+BF16_RANK_ROW_SETS = {64: 8, 128: 8, 256: 4, 512: 2}      # csrc/a4r_eval.hip: RankBf16Shape -- 16-user row sets a workgroup of a4r_eval_rank_bf16 holds
+BF16_PEAK_TF = 2500.0
+
+
+def bf16_leg(a, dev):
+    """--bf16: a4r_eval_rank_bf16 beside a4r_eval_rank / a4r_eval_rank_cand of the same build on the same random tables, kernels only: 32 768 users
+    (--users), 65 537 items at E = 64 .. 512 and 500 001 items at E = 64 / 128, the candidate set off and at 0.1.  Legs, interleaved over three
+    rounds after a warm-up of each, device events around ``reps`` calls: fp32; bf16 (operands cast beforehand); bf16_cast (the table's and the
+    users' casts inside the timed region: what one evaluation batch pays).  Per leg the minimum and the spread (max - min) / min of the rounds,
+    the table bytes per second (table bytes x passes: one pass per 16 users in fp32, per 16 x row sets in bf16) and, for bf16, the share of the
+    2.5 PF bf16 MFMA peak.  Also the agreement of the two on the same data: largest |rank change|, HR@10 / nDCG@10 of both (logged, not asserted).
+    One JSON line per configuration, appended to --json."""
+    from adapter4rec_amd import _lib as L
+    U, rounds = a.users, 3
+    g = torch.Generator(device=dev).manual_seed(B.SEED)
+    box = torch.cuda.get_device_name(0)
+    out = open(a.json, 'a') if a.json else None
+    for N1, E in ((65537, 64), (65537, 128), (65537, 256), (65537, 512), (500001, 64), (500001, 128)):
+        reps = 5 if N1 < 100000 else 2
+        emb = torch.randn(N1, E, device=dev, generator=g)
+        prec = torch.randn(U, E, device=dev, generator=g)
+        target = torch.randint(1, N1, (U,), device=dev, dtype=torch.int32, generator=g)
+        ptr = torch.arange(0, U + 1, device=dev, dtype=torch.int32) * 20
+        hidx = torch.randint(1, N1, (U * 20 + 1,), device=dev, dtype=torch.int32, generator=g)
+        emb_b = torch.empty(N1, E, dtype=torch.bfloat16, device=dev)
+        prec_b = torch.empty(U, E, dtype=torch.bfloat16, device=dev)
+        L.cast_bf16(emb, emb_b)
+        L.cast_bf16(prec, prec_b)
+        r32 = torch.zeros(U, dtype=torch.int32, device=dev)
+        rb = torch.zeros(U, dtype=torch.int32, device=dev)
+        for fraction in (None, 0.1):
+            cand = None if fraction is None else (torch.rand(N1, device=dev, generator=g) < fraction).to(torch.uint8).contiguous()
+
+            def fp32():
+                L.eval_rank(prec, emb, target, ptr, hidx, r32) if cand is None else L.eval_rank_cand(prec, emb, target, ptr, hidx, cand, r32)
+
+            def bf16():
+                L.eval_rank_bf16(prec_b, emb_b, target, ptr, hidx, rb, cand)
+
+            def bf16_cast():
+                L.cast_bf16(emb, emb_b)
+                L.cast_bf16(prec, prec_b)
+                L.eval_rank_bf16(prec_b, emb_b, target, ptr, hidx, rb, cand)
+            legs = dict(fp32=fp32, bf16=bf16, bf16_cast=bf16_cast)
+            for fn in legs.values():
+                fn()
+                fn()
+            us = {k: [] for k in legs}
+            for _ in range(rounds):
+                for k, fn in legs.items():
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    for _ in range(reps):
+                        fn()
+                    e1.record()
+                    torch.cuda.synchronize()
+                    us[k].append(round(e0.elapsed_time(e1) / reps * 1e3, 1))
+            best = {k: min(v) for k, v in us.items()}
+            spread = {k: round((max(v) - min(v)) / min(v), 4) for k, v in us.items()}
+            a32, ab = r32.float(), rb.float()
+            metrics = lambda r: [round(float((r <= 10).float().mean()), 6), round(float(torch.where(r <= 10, 1 / torch.log2(r + 1), torch.zeros_like(r)).mean()), 6)]
+            passes32, passes_b = (U + 15) // 16, (U + 16 * BF16_RANK_ROW_SETS[E] - 1) // (16 * BF16_RANK_ROW_SETS[E])
+            line = dict(bench='eval_rank', box=box, users=U, items=N1, E=E, fraction=fraction, rounds=rounds, reps=reps, row_sets=BF16_RANK_ROW_SETS[E],
+                        fp32_us=best['fp32'], bf16_us=best['bf16'], bf16_cast_us=best['bf16_cast'], all_us=us, spread=spread,
+                        fp32_over_bf16=round(best['fp32'] / best['bf16'], 2), fp32_over_bf16_cast=round(best['fp32'] / best['bf16_cast'], 2),
+                        fp32_table_TB_per_s=round(N1 * E * 4 * passes32 / best['fp32'] / 1e6, 2),
+                        bf16_table_TB_per_s=round(N1 * E * 2 * passes_b / best['bf16'] / 1e6, 2),
+                        bf16_share_of_mfma_peak=round(2.0 * U * N1 * E / best['bf16'] / 1e6 / BF16_PEAK_TF, 4),
+                        ranks_equal=round(float((r32 == rb).float().mean()), 4), largest_rank_change=int((r32 - rb).abs().max()),
+                        median_rank_change=float((a32 - ab).abs().median()), hr10_ndcg10_fp32=metrics(a32), hr10_ndcg10_bf16=metrics(ab))
+            print(json.dumps(line), flush=True)
+            if out:
+                out.write(json.dumps(line) + '\n')
+                out.flush()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--items', type=int, default=65536)
@@ -158,9 +236,13 @@ def main():
                     help='run the candidate-set leg instead: a4r_eval_rank_cand beside a4r_eval_rank under a random mask of this fraction')
     ap.add_argument('--sampled', type=int, nargs='+', default=None, metavar='N',
                     help='run the sampled-evaluation leg instead: a4r_eval_rank_sampled beside draw + rank_lists, the full sweep and eager torch, at N negatives')
+    ap.add_argument('--bf16', action='store_true',
+                    help='run the bf16-score leg instead: a4r_eval_rank_bf16 beside a4r_eval_rank / a4r_eval_rank_cand, with and without the casts')
     a = ap.parse_args()
     dev = torch.device('cuda', 0)
     torch.cuda.set_device(0)
+    if a.bf16:
+        return bf16_leg(a, dev)
     if a.candidates is not None:
         return candidates_leg(a, dev)
     if a.sampled is not None:

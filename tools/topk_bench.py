@@ -2,7 +2,11 @@
 """Top-K recommendation on one MI355X: a4r_topk_items beside a4r_eval_rank (the same scoring sweep, one rank per user) and beside the torch path a
 user would otherwise write (chunked fp32 matmul, history masked, torch.topk), and recommend() end to end -- one JSON line per configuration.
 
-    python tools/topk_bench.py [--iters N] [--only NAME] [--candidates FRACTION] [--lists C] [--mmr] [--similar]
+    python tools/topk_bench.py [--iters N] [--only NAME] [--candidates FRACTION] [--lists C] [--mmr] [--similar] [--bf16]
+
+--bf16 runs the bf16-score leg instead (bf16_cfg): a4r_topk_items_bf16 beside a4r_topk_items / a4r_topk_items_cand of the same build, 32 768 users,
+65 537 items at E = 64 .. 512 and 500 001 items at E = 64 / 128, K = 10 / 100 / 256, the candidate set off and at 0.1, the casts in one leg and outside
+another, interleaved rounds after a warm-up (the numbers land in profiles/score_bf16_bench.jsonl).
 
 --candidates FRACTION runs the candidate-set leg instead (cand_cfg): a4r_topk_items_cand / a4r_eval_rank_cand beside the unmasked entries, interleaved.
 --lists C runs the per-user-list leg instead (lists_cfg): a4r_topk_lists over C listed items per user (C = 0: 100, 1000 and 4096 in turn), E = 64 and
@@ -270,6 +274,62 @@ def similar_cfg(name, Q, N1, E, k, iters, rounds=3):
                 id_agreement_with_eager=round(float((ei.int() == ids).float().mean()), 6))
 
 
+def bf16_row_sets(E, k):
+    """csrc/a4r_topk.hip: topk_bf16_rs -- the 16-user row sets a workgroup of a4r_topk_items_bf16 holds"""
+    return 2 if k <= 64 and E in (128, 256) else 1
+
+
+def bf16_cfg(name, U, N1, E, k, fraction, iters, rounds=3, H=20):
+    """--bf16: a4r_topk_items_bf16 beside a4r_topk_items / a4r_topk_items_cand of the same build on the same random data.  Legs, interleaved
+    `rounds` times after a warm-up of each: fp32; bf16 (operands cast beforehand); bf16_cast (the table's and the users' casts inside the timed
+    region).  Per leg every round's mean, the minimum's ratio and the spread (max - min) / min; the table bytes per second (table bytes x passes:
+    one pass per 16 users in fp32, per 16 x row sets in bf16; at K >= 100 the time goes to sort-and-cut rounds as well) and the bf16 leg's share
+    of the 2.5 PF bf16 MFMA peak; and how the two lists differ on this data (logged, not asserted): the share of users whose lists are identical,
+    and the share of list positions holding the same id."""
+    from adapter4rec_amd import _lib as L
+    emb, prec, hist, ptr, tgt = data(U, N1, E, H)
+    flat = hist.reshape(-1).contiguous()
+    cand = None
+    if fraction is not None:
+        g = torch.Generator(device=DEV).manual_seed(1)
+        cand = (torch.rand(N1, device=DEV, generator=g) < fraction).to(torch.uint8).contiguous()
+    emb_b = torch.empty(N1, E, dtype=torch.bfloat16, device=DEV)
+    prec_b = torch.empty(U, E, dtype=torch.bfloat16, device=DEV)
+    L.cast_bf16(emb, emb_b)
+    L.cast_bf16(prec, prec_b)
+    ids = torch.empty(U, k, dtype=torch.int32, device=DEV)
+    sc = torch.empty(U, k, dtype=torch.float32, device=DEV)
+    ids_b, sc_b = torch.empty_like(ids), torch.empty_like(sc)
+
+    def fp32():
+        L.topk_items(prec, emb, ptr, flat, k, ids, sc) if cand is None else L.topk_items_cand(prec, emb, ptr, flat, cand, k, ids, sc)
+
+    def bf16():
+        L.topk_items_bf16(prec_b, emb_b, ptr, flat, k, ids_b, sc_b, cand)
+
+    def bf16_cast():
+        L.cast_bf16(emb, emb_b)
+        L.cast_bf16(prec, prec_b)
+        L.topk_items_bf16(prec_b, emb_b, ptr, flat, k, ids_b, sc_b, cand)
+    legs = dict(fp32=fp32, bf16=bf16, bf16_cast=bf16_cast)
+    for fn in legs.values():                                        # warm-up: every leg once before any is timed
+        fn()
+    ms = {n: [] for n in legs}
+    for _ in range(rounds):
+        for n, fn in legs.items():
+            ms[n].append(round(timed(fn, iters), 4))
+    best = {n: min(v) for n, v in ms.items()}
+    spread = {n: round((max(v) - min(v)) / min(v), 4) for n, v in ms.items()}
+    rs = bf16_row_sets(E, k)
+    return dict(bench='topk', name=name, box=torch.cuda.get_device_name(0), users=U, items=N1, E=E, k=k, fraction=fraction, rounds=rounds, iters=iters,
+                row_sets=rs, **{n + '_ms': v for n, v in ms.items()}, spread=spread, fp32_over_bf16=round(best['fp32'] / best['bf16'], 2),
+                fp32_over_bf16_cast=round(best['fp32'] / best['bf16_cast'], 2),
+                fp32_table_TB_per_s=round(N1 * E * 4 * ((U + 15) // 16) / best['fp32'] / 1e9, 2),
+                bf16_table_TB_per_s=round(N1 * E * 2 * ((U + 16 * rs - 1) // (16 * rs)) / best['bf16'] / 1e9, 2),
+                bf16_share_of_mfma_peak=round(2.0 * U * N1 * E / best['bf16'] / 1e9 / 2500.0, 4),
+                identical_lists=round(float((ids == ids_b).all(1).float().mean()), 4), same_id_positions=round(float((ids == ids_b).float().mean()), 4))
+
+
 def recommend_cfg(name, U, item_num, k, iters, T=20):
     from adapter4rec_amd.cv import Model
     from adapter4rec_amd.cv.data_utils import get_itemId_embeddings
@@ -302,7 +362,18 @@ def main():
                     help='run the re-ranking leg instead: a4r_mmr_rerank beside the eager gather + bmm + K-round loop, pools of 100 and 256, E = 64 and 128')
     ap.add_argument('--similar', action='store_true',
                     help='run the similar-items leg instead: a4r_topk_similar beside the composition of existing entries and eager torch, K = 10 and 100, E = 64 and 128')
+    ap.add_argument('--bf16', action='store_true',
+                    help='run the bf16-score leg instead: a4r_topk_items_bf16 beside the fp32 entries, K = 10 / 100 / 256, E = 64 .. 512, candidates off and at 0.1')
     a = ap.parse_args()
+    if a.bf16:
+        for N1, widths, it in ((65537, (64, 128, 256, 512), a.iters), (500001, (64, 128), max(1, a.iters // 4))):
+            for E in widths:
+                for k in (10, 100, 256):
+                    for fraction in (None, 0.1):
+                        name = f'bf16_k{k}_e{E}_{N1}' + ('' if fraction is None else '_cand')
+                        if not a.only or a.only == name:
+                            print(json.dumps(bf16_cfg(name, 32768, N1, E, k, fraction, it)), flush=True)
+        return
     if a.similar:
         for k in (10, 100):
             for E in (64, 128):
