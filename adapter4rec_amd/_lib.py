@@ -872,35 +872,62 @@ def topk_items(prec, item_emb, excl_ptr, excl_idx, k, ids, scores):
     excl_idx[excl_ptr[u] .. excl_ptr[u + 1]) (<= EVAL_MAX_HISTORY ids each: the caller checks, as for eval_rank), by score descending, ties by
     smaller id; short lists end in id 0 / -inf (include/a4r.h).  The workspace is allocated here."""
     require_gpu(prec, item_emb, excl_ptr, excl_idx, ids, scores)
-    k = int(k)
-    if prec.dim() != 2 or item_emb.dim() != 2 or prec.shape[1] != item_emb.shape[1]:
-        raise ValueError(f'topk_items: prec [U, E] and item_emb [N1, E] expected, got {tuple(prec.shape)} and {tuple(item_emb.shape)}')
-    U, E = prec.shape
-    N1 = item_emb.shape[0]
-    if prec.dtype != torch.float32 or item_emb.dtype != torch.float32 or not prec.is_contiguous() or not item_emb.is_contiguous():
-        raise ValueError('topk_items: prec and item_emb must be contiguous fp32')
-    if E not in TOPK_E:
-        raise ValueError(f'topk_items: E = {E}, supported {TOPK_E}')
-    if not 1 <= k <= TOPK_MAX_K:
-        raise ValueError(f'topk_items: k = {k} outside 1 .. {TOPK_MAX_K}')
-    if U < 1 or N1 < 2:
-        raise ValueError(f'topk_items: U = {U} users and N1 = {N1} table rows (row 0 = the pad item): need U >= 1, N1 >= 2')
-    if (prec.data_ptr() | item_emb.data_ptr()) & 15:
-        raise ValueError('topk_items: prec and item_emb must be 16-byte aligned')
-    for name, t in (('excl_ptr', excl_ptr), ('excl_idx', excl_idx), ('ids', ids)):
-        if t.dtype != torch.int32 or not t.is_contiguous():
-            raise ValueError(f'topk_items: {name} must be contiguous int32')
-    if scores.dtype != torch.float32 or not scores.is_contiguous():
-        raise ValueError('topk_items: scores must be contiguous fp32')
-    if excl_ptr.numel() != U + 1:
-        raise ValueError(f'topk_items: excl_ptr must hold U + 1 = {U + 1} offsets, got {excl_ptr.numel()}')
-    if tuple(ids.shape) != (U, k) or tuple(scores.shape) != (U, k):
-        raise ValueError(f'topk_items: ids and scores must be [{U}, {k}]')
-    if excl_idx.numel() == 0:                 # (an empty list has no data pointer; the kernel reads no id of it)
-        excl_idx = torch.zeros(1, dtype=torch.int32, device=prec.device)
-    ws = torch.empty(topk_ws_bytes(U, N1, k), dtype=torch.uint8, device=prec.device)
+    U, N1, E = _sweep_operands('topk_items', torch.float32, prec, item_emb)
+    k, excl_idx, ws = _topk_args('topk_items', prec.device, U, excl_ptr, excl_idx, k, ids, scores, lambda k: topk_ws_bytes(U, N1, k))
     _check(lib().a4r_topk_items(_stream(), _p(prec), _p(item_emb), _p(excl_ptr), _p(excl_idx), _p(ids), _p(scores), _p(ws), U, N1, E, k), 'a4r_topk_items')
     return ids, scores
+
+
+def _sweep_operands(what, dtype, prec, table):
+    """The operands of an item-table sweep, prec [U, E] and the table [N1, E], checked for the wrapper `what` (topk_items, topk_items_cand: fp32;
+    topk_items_bf16, eval_rank_bf16: bf16, under their own names) -> U, N1, E.  A wrapper
+    with a candidate mask checks it behind this, once N1 stands, and in front of _topk_args."""
+    a, b, spelt = ('prec', 'item_emb', 'fp32') if dtype == torch.float32 else ('prec_b', 'table_b', 'bf16 (the copies cast_bf16 writes)')
+    if prec.dim() != 2 or table.dim() != 2 or prec.shape[1] != table.shape[1]:
+        raise ValueError(f'{what}: {a} [U, E] and {b} [N1, E] expected, got {tuple(prec.shape)} and {tuple(table.shape)}')
+    U, E = prec.shape
+    N1 = table.shape[0]
+    if prec.dtype != dtype or table.dtype != dtype or not prec.is_contiguous() or not table.is_contiguous():
+        raise ValueError(f'{what}: {a} and {b} must be contiguous {spelt}')
+    if E not in TOPK_E:
+        raise ValueError(f'{what}: E = {E}, supported {TOPK_E}')
+    if U < 1 or N1 < 2:
+        raise ValueError(f'{what}: U = {U} users and N1 = {N1} table rows (row 0 = the pad item): need U >= 1, N1 >= 2')
+    if (prec.data_ptr() | table.data_ptr()) & 15:
+        raise ValueError(f'{what}: {a} and {b} must be 16-byte aligned')
+    return U, N1, E
+
+
+def _topk_k(what, k):
+    k = int(k)
+    if not 1 <= k <= TOPK_MAX_K:
+        raise ValueError(f'{what}: k = {k} outside 1 .. {TOPK_MAX_K}')
+    return k
+
+
+def _topk_outputs(what, rows, k, ids, scores, f32='fp32'):
+    """The outputs of a top-K wrapper: ids int32 / scores fp32 (spelt f32 in the wrapper's messages), contiguous [rows, k]"""
+    if ids.dtype != torch.int32 or not ids.is_contiguous():
+        raise ValueError(f'{what}: ids must be contiguous int32')
+    if scores.dtype != torch.float32 or not scores.is_contiguous():
+        raise ValueError(f'{what}: scores must be contiguous {f32}')
+    if tuple(ids.shape) != (rows, k) or tuple(scores.shape) != (rows, k):
+        raise ValueError(f'{what}: ids and scores must be [{rows}, {k}]')
+
+
+def _topk_args(what, device, U, excl_ptr, excl_idx, k, ids, scores, ws_bytes):
+    """What topk_items, topk_items_cand and topk_items_bf16 do between their operand checks and their call: the checks of k, the CSR exclusion
+    lists and the outputs, a stand-in for an empty excl_idx, the workspace of ws_bytes(k) bytes (the wrapper's own query) -> k, excl_idx, ws"""
+    k = _topk_k(what, k)
+    for name, t in (('excl_ptr', excl_ptr), ('excl_idx', excl_idx)):
+        if t.dtype != torch.int32 or not t.is_contiguous():
+            raise ValueError(f'{what}: {name} must be contiguous int32')
+    if excl_ptr.numel() != U + 1:
+        raise ValueError(f'{what}: excl_ptr must hold U + 1 = {U + 1} offsets, got {excl_ptr.numel()}')
+    _topk_outputs(what, U, k, ids, scores)
+    if excl_idx.numel() == 0:                 # (an empty list has no data pointer; the kernel reads no id of it)
+        excl_idx = torch.zeros(1, dtype=torch.int32, device=device)
+    return k, excl_idx, torch.empty(ws_bytes(k), dtype=torch.uint8, device=device)
 
 
 def eval_rank(prec, item_emb, target, hist_ptr, hist_idx, rank):

@@ -44,34 +44,9 @@ def topk_items_cand(prec, item_emb, excl_ptr, excl_idx, cand, k, ids, scores):
     """a4r_topk_items_cand: topk_items over the items i with cand[i] != 0 (uint8 / bool [N1] on the device, cand[0] ignored) that are not in the
     user's exclusion list; everything else, the argument checks and the workspace allocated here included, as topk_items."""
     L.require_gpu(prec, item_emb, excl_ptr, excl_idx, ids, scores)
-    k = int(k)
-    if prec.dim() != 2 or item_emb.dim() != 2 or prec.shape[1] != item_emb.shape[1]:
-        raise ValueError(f'topk_items_cand: prec [U, E] and item_emb [N1, E] expected, got {tuple(prec.shape)} and {tuple(item_emb.shape)}')
-    U, E = prec.shape
-    N1 = item_emb.shape[0]
+    U, N1, E = L._sweep_operands('topk_items_cand', torch.float32, prec, item_emb)
     cand = candidate_mask(cand, N1, 'topk_items_cand')
-    if prec.dtype != torch.float32 or item_emb.dtype != torch.float32 or not prec.is_contiguous() or not item_emb.is_contiguous():
-        raise ValueError('topk_items_cand: prec and item_emb must be contiguous fp32')
-    if E not in L.TOPK_E:
-        raise ValueError(f'topk_items_cand: E = {E}, supported {L.TOPK_E}')
-    if not 1 <= k <= L.TOPK_MAX_K:
-        raise ValueError(f'topk_items_cand: k = {k} outside 1 .. {L.TOPK_MAX_K}')
-    if U < 1 or N1 < 2:
-        raise ValueError(f'topk_items_cand: U = {U} users and N1 = {N1} table rows (row 0 = the pad item): need U >= 1, N1 >= 2')
-    if (prec.data_ptr() | item_emb.data_ptr()) & 15:
-        raise ValueError('topk_items_cand: prec and item_emb must be 16-byte aligned')
-    for name, t in (('excl_ptr', excl_ptr), ('excl_idx', excl_idx), ('ids', ids)):
-        if t.dtype != torch.int32 or not t.is_contiguous():
-            raise ValueError(f'topk_items_cand: {name} must be contiguous int32')
-    if scores.dtype != torch.float32 or not scores.is_contiguous():
-        raise ValueError('topk_items_cand: scores must be contiguous fp32')
-    if excl_ptr.numel() != U + 1:
-        raise ValueError(f'topk_items_cand: excl_ptr must hold U + 1 = {U + 1} offsets, got {excl_ptr.numel()}')
-    if tuple(ids.shape) != (U, k) or tuple(scores.shape) != (U, k):
-        raise ValueError(f'topk_items_cand: ids and scores must be [{U}, {k}]')
-    if excl_idx.numel() == 0:                 # (an empty list has no data pointer; the kernel reads no id of it)
-        excl_idx = torch.zeros(1, dtype=torch.int32, device=prec.device)
-    ws = torch.empty(L.topk_ws_bytes(U, N1, k), dtype=torch.uint8, device=prec.device)
+    k, excl_idx, ws = L._topk_args('topk_items_cand', prec.device, U, excl_ptr, excl_idx, k, ids, scores, lambda k: L.topk_ws_bytes(U, N1, k))
     L._check(L.lib().a4r_topk_items_cand(L._stream(), L._p(prec), L._p(item_emb), L._p(excl_ptr), L._p(excl_idx), L._p(cand), L._p(ids), L._p(scores),
                                          L._p(ws), U, N1, E, k), 'a4r_topk_items_cand')
     return ids, scores

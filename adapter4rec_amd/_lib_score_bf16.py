@@ -24,27 +24,11 @@ def topk_bf16_ws_bytes(U, N1, E, k):
     return int(L.lib().a4r_topk_bf16_ws_bytes(U, N1, E, k))
 
 
-def _operands(what, prec_b, table_b):
-    if prec_b.dim() != 2 or table_b.dim() != 2 or prec_b.shape[1] != table_b.shape[1]:
-        raise ValueError(f'{what}: prec_b [U, E] and table_b [N1, E] expected, got {tuple(prec_b.shape)} and {tuple(table_b.shape)}')
-    U, E = prec_b.shape
-    N1 = table_b.shape[0]
-    if prec_b.dtype != torch.bfloat16 or table_b.dtype != torch.bfloat16 or not prec_b.is_contiguous() or not table_b.is_contiguous():
-        raise ValueError(f'{what}: prec_b and table_b must be contiguous bf16 (the copies cast_bf16 writes)')
-    if E not in L.TOPK_E:
-        raise ValueError(f'{what}: E = {E}, supported {L.TOPK_E}')
-    if U < 1 or N1 < 2:
-        raise ValueError(f'{what}: U = {U} users and N1 = {N1} table rows (row 0 = the pad item): need U >= 1, N1 >= 2')
-    if (prec_b.data_ptr() | table_b.data_ptr()) & 15:
-        raise ValueError(f'{what}: prec_b and table_b must be 16-byte aligned')
-    return U, N1, E
-
-
 def eval_rank_bf16(prec_b, table_b, target, hist_ptr, hist_idx, rank, cand=None):
     """a4r_eval_rank_bf16: eval_rank (cand None) or eval_rank_cand (cand uint8 / bool [N1] on the device) with score(u, i) = <prec_b[u], table_b[i]>
     from the bf16 MFMA, accumulated in fp32 (include/a4r_score_bf16.h).  prec_b [U, E], table_b [N1, E]: contiguous bf16."""
     L.require_gpu(prec_b, table_b, target, hist_ptr, hist_idx, rank)
-    U, N1, E = _operands('eval_rank_bf16', prec_b, table_b)
+    U, N1, E = L._sweep_operands('eval_rank_bf16', torch.bfloat16, prec_b, table_b)
     if cand is not None:
         cand = candidate_mask(cand, N1, 'eval_rank_bf16')
     for name, t, n in (('target', target, U), ('hist_ptr', hist_ptr, U + 1), ('hist_idx', hist_idx, 1), ('rank', rank, U)):
@@ -58,24 +42,10 @@ def topk_items_bf16(prec_b, table_b, excl_ptr, excl_idx, k, ids, scores, cand=No
     """a4r_topk_items_bf16: topk_items (cand None) or topk_items_cand (cand uint8 / bool [N1] on the device) with the scores of eval_rank_bf16 --
     the same bits.  Everything else, the argument checks and the workspace allocated here included, as topk_items."""
     L.require_gpu(prec_b, table_b, excl_ptr, excl_idx, ids, scores)
-    k = int(k)
-    U, N1, E = _operands('topk_items_bf16', prec_b, table_b)
+    U, N1, E = L._sweep_operands('topk_items_bf16', torch.bfloat16, prec_b, table_b)
     if cand is not None:
         cand = candidate_mask(cand, N1, 'topk_items_bf16')
-    if not 1 <= k <= L.TOPK_MAX_K:
-        raise ValueError(f'topk_items_bf16: k = {k} outside 1 .. {L.TOPK_MAX_K}')
-    for name, t in (('excl_ptr', excl_ptr), ('excl_idx', excl_idx), ('ids', ids)):
-        if t.dtype != torch.int32 or not t.is_contiguous():
-            raise ValueError(f'topk_items_bf16: {name} must be contiguous int32')
-    if scores.dtype != torch.float32 or not scores.is_contiguous():
-        raise ValueError('topk_items_bf16: scores must be contiguous fp32')
-    if excl_ptr.numel() != U + 1:
-        raise ValueError(f'topk_items_bf16: excl_ptr must hold U + 1 = {U + 1} offsets, got {excl_ptr.numel()}')
-    if tuple(ids.shape) != (U, k) or tuple(scores.shape) != (U, k):
-        raise ValueError(f'topk_items_bf16: ids and scores must be [{U}, {k}]')
-    if excl_idx.numel() == 0:                 # (an empty list has no data pointer; the kernel reads no id of it)
-        excl_idx = torch.zeros(1, dtype=torch.int32, device=prec_b.device)
-    ws = torch.empty(topk_bf16_ws_bytes(U, N1, E, k), dtype=torch.uint8, device=prec_b.device)
+    k, excl_idx, ws = L._topk_args('topk_items_bf16', prec_b.device, U, excl_ptr, excl_idx, k, ids, scores, lambda k: topk_bf16_ws_bytes(U, N1, E, k))
     L._check(L.lib().a4r_topk_items_bf16(L._stream(), L._p(prec_b), L._p(table_b), L._p(excl_ptr), L._p(excl_idx), L._p(cand), L._p(ids), L._p(scores),
                                          L._p(ws), U, N1, E, k), 'a4r_topk_items_bf16')
     return ids, scores

@@ -53,14 +53,12 @@ def topk_similar(item_emb, inv_norm, query, cand, min_sim, k, ids, scores):
     a query with a zero or non-finite row, gets pads only (include/a4r_similar.h).  The workspace is allocated here, as topk_items allocates it."""
     L.require_gpu(item_emb, inv_norm, query, cand, ids, scores)
     what = 'topk_similar'
-    k = int(k)
     min_sim = -math.inf if min_sim is None else float(min_sim)
     N1, E = _table(what, item_emb)
     if query.dim() != 1 or query.dtype != torch.int32 or not query.is_contiguous():
         raise ValueError(f'{what}: query must be contiguous int32 [Q], got {query.dtype} {tuple(query.shape)}')
     Q = query.numel()
-    if not 1 <= k <= L.TOPK_MAX_K:
-        raise ValueError(f'{what}: k = {k} outside 1 .. {L.TOPK_MAX_K}')
+    k = L._topk_k(what, k)
     if Q < 1 or N1 < 2:
         raise ValueError(f'{what}: Q = {Q} queries and N1 = {N1} table rows (row 0 = the pad item): need Q >= 1, N1 >= 2')
     if inv_norm is not None and (inv_norm.dtype != torch.float32 or not inv_norm.is_contiguous() or tuple(inv_norm.shape) != (N1,)):
@@ -72,12 +70,7 @@ def topk_similar(item_emb, inv_norm, query, cand, min_sim, k, ids, scores):
             cand = cand.view(torch.uint8)
     if math.isnan(min_sim):
         raise ValueError(f'{what}: min_sim is NaN')
-    if ids.dtype != torch.int32 or not ids.is_contiguous():
-        raise ValueError(f'{what}: ids must be contiguous int32')
-    if scores.dtype != torch.float32 or not scores.is_contiguous():
-        raise ValueError(f'{what}: scores must be contiguous float32')
-    if tuple(ids.shape) != (Q, k) or tuple(scores.shape) != (Q, k):
-        raise ValueError(f'{what}: ids and scores must be [{Q}, {k}]')
+    L._topk_outputs(what, Q, k, ids, scores, f32='float32')
     ws = torch.empty(L.topk_ws_bytes(Q, N1, k), dtype=torch.uint8, device=item_emb.device)
     L._check(L.lib().a4r_topk_similar(L._stream(), L._p(item_emb), L._p(inv_norm), L._p(query), L._p(cand), min_sim, L._p(ids), L._p(scores), L._p(ws),
                                       Q, N1, E, k), 'a4r_topk_similar')

@@ -45,27 +45,7 @@ __device__ __forceinline__ void draw_setup(DrawLds& L, const int32_t* __restrict
     }
     if (tid == 0) L.raw[nx] = is_item(t, N1) ? t : 0;
     __syncthreads();
-    {   // ascending order: the rank of each id among the n, ties by position (a permutation: every slot is written once)
-        int v[DPER], pos[DPER];
-#pragma unroll
-        for (int q = 0; q < DPER; ++q) {
-            const int j = tid + 256 * q;
-            pos[q] = -1; v[q] = 0;
-            if (j < n) {
-                const int x = L.raw[j];
-                int r = 0;
-                for (int k = 0; k < n; ++k) {
-                    const int y = L.raw[k];
-                    r += (y < x || (y == x && k < j)) ? 1 : 0;
-                }
-                v[q] = x; pos[q] = r;
-            }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int q = 0; q < DPER; ++q)
-            if (pos[q] >= 0) L.raw[pos[q]] = v[q];
-    }
+    rank_sort_i32<DPER, 256>(L.raw, n, tid);
     __syncthreads();
     int d = 0;                                       // the first of every run of equal non-zero ids, numbered in order
 #pragma unroll

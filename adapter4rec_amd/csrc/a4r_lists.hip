@@ -4,7 +4,7 @@
 // nothing to share here.
 //
 // One 256-thread workgroup per user (grid-stride over users).
-//   Set-up.  The user's exclusion / history ids are copied to LDS and put in ascending order (the rank sort of topk_partial_kernel); every lane
+//   Set-up.  The user's exclusion / history ids are copied to LDS and put in ascending order (rank_sort_i32 of a4r_select.h); every lane
 //   keeps its E / 16 floats of the user's prec row in registers.
 //   Gather and score.  Sixteen lanes own one listed row: lane l reads the 16-byte chunks l, l + 16, ... of the row (one 256-byte line per load
 //   of the group), multiplies them into its own accumulator in sequence (fma), and the 16 accumulators meet in a four-step xor butterfly --
@@ -12,7 +12,7 @@
 //   (8 .. 16 loads of 16 bytes per lane) before it uses the first, and the ids of the next RF rows before that: the loop waits on memory, not
 //   on arithmetic.  A row whose id is no item (0, negative, >= N1) is not requested at all.
 //   Keys.  Lane r of the group takes the r-th of its RF rows (every lane holds every sum): it searches the exclusion list and writes the row's
-//   64-bit key (a4r_topk_key.h), or 0, to keys[j] in LDS, j = the row's place in the list -- RF searches side by side, not one after the other.  The tail up to the next power of two (at least 64) is zeroed and the keys are sorted descending, bitonic, in LDS,
+//   64-bit key (a4r_select.h), or 0, to keys[j] in LDS, j = the row's place in the list -- RF searches side by side, not one after the other.  The tail up to the next power of two (at least 64) is zeroed and the keys are sorted descending, bitonic, in LDS,
 //   up to four steps of the network per LDS round trip (bitonic_pass).
 //   An id listed twice gave the same key twice (the score is a pure function), and equal keys are now adjacent: a key is kept if it is not 0
 //   and differs from its left neighbour.
@@ -63,27 +63,7 @@ __global__ void __launch_bounds__(256) lists_kernel(const float* __restrict__ pr
             }
         }
         __syncthreads();
-        {   // the exclusion ids in ascending order: the rank of each id among the list, ties by position
-            int v[XPER], pos[XPER];
-#pragma unroll
-            for (int m = 0; m < XPER; ++m) {
-                const int j = tid + 256 * m;
-                pos[m] = -1; v[m] = 0;
-                if (j < nx) {
-                    const int x = excl[j];
-                    int q = 0;
-                    for (int k = 0; k < nx; ++k) {
-                        const int y = excl[k];
-                        q += (y < x || (y == x && k < j)) ? 1 : 0;
-                    }
-                    v[m] = x; pos[m] = q;
-                }
-            }
-            __syncthreads();
-#pragma unroll
-            for (int m = 0; m < XPER; ++m)
-                if (pos[m] >= 0) excl[pos[m]] = v[m];
-        }
+        rank_sort_i32<XPER, 256>(excl, nx, tid);     // the exclusion ids in ascending order
         __syncthreads();
         for (int base = 0; base < n; base += 16 * RF) {
             int id[RF];
@@ -112,14 +92,7 @@ __global__ void __launch_bounds__(256) lists_kernel(const float* __restrict__ pr
             const int j = base + l16 * 16 + g;
             if (l16 < RF && j < n) {
                 uint64_t key = 0;
-                if (my_ok) {
-                    int lo = 0, hi = nx;
-                    while (lo < hi) {
-                        const int mid = (lo + hi) >> 1;
-                        if (excl[mid] < my_id) lo = mid + 1; else hi = mid;
-                    }
-                    if (!(lo < nx && excl[lo] == my_id)) key = topk_key(my_s, my_id);
-                }
+                if (my_ok && !sorted_has(excl, nx, my_id)) key = topk_key(my_s, my_id);
                 keys[kslot(j)] = key;
             }
         }

@@ -3,7 +3,7 @@
 // bitonic sort in LDS.  One definition, so the two files cannot drift apart: a sampled evaluation replays bit for bit through the list kernels.
 #pragma once
 #include "a4r_score_sweep.h"
-#include "a4r_topk_key.h"
+#include "a4r_select.h"
 #include "../../include/a4r.h"
 
 namespace {

@@ -18,8 +18,15 @@
 //
 // Similar items (a4r_topk_similar, include/a4r_similar.h).  similar_partial_kernel is the same sweep and selection with the 16 rows of a workgroup
 // taken from the item table itself; compaction, merge and decode are the ones above, shared as they are.  a4r_row_inv_norms lives here too.
+//
+// Where the pieces live.  The key, its decoding, the rank sort of an id list and the search of the sorted list: a4r_select.h, shared with the list
+// kernels.  Here, one copy each for the three partial kernels (fp32, bf16, similar), which keep their own loads and MFMA chains:
+// topk_append (with the trigger protocol), topk_step_end, topk_write_out and topk_compact; on the host topk_args_ok (every export's checks) and
+// topk_finish (decode or merge).  The two kernels with exclusion lists write the sort and the search of
+// a4r_select.h out: timed through the helpers they lost 0.4 - 1 % (profiles/LOG.md).
+#include <initializer_list>
 #include "a4r_score_sweep.h"
-#include "a4r_topk_key.h"
+#include "a4r_select.h"
 #include "../../include/a4r.h"
 
 namespace {
@@ -28,7 +35,7 @@ constexpr int MAXX = A4R_EVAL_MAX_HISTORY;   // exclusion ids per user kept in L
 constexpr int STEP_KEYS = 64;                // keys a step can add per user: 4 waves x 16 item columns
 constexpr int MAX_RANGES = 32;               // item ranges per user: the merge holds gy x K <= 32 x 256 keys (64 KiB) in LDS
 
-// topk_key / topk_emit: a4r_topk_key.h (shared with a4r_lists.hip)
+// topk_key / topk_emit, rank_sort_i32 / sorted_has: a4r_select.h (shared with a4r_lists.hip and a4r_eval_negatives.hip)
 
 // Sort each of the 16 buffers (cap keys, cap a power of two) descending, entries past the count as 0; keep the best K, reset the thresholds.
 __device__ void topk_compact(uint64_t* buf, int cap, int K, int32_t* cnt, uint64_t* thr) {
@@ -55,6 +62,49 @@ __device__ void topk_compact(uint64_t* buf, int cap, int K, int32_t* cnt, uint64
     __syncthreads();
 }
 
+// The pieces the three partial kernels below are made of.  A row set is 16 rows (users, or query items) of a workgroup with their LDS: 16 buffers
+// of cap keys, cnt[16] and thr_s[16].  A kernel with several row sets passes the
+// first set's pointers; set rs is 16 rs rows further on.
+
+// Append and trigger: the key goes to the next free slot of row ul's buffer (ul counts over all row sets).  Slot p < cap: a step adds at most
+// STEP_KEYS keys per row, and whenever a step leaves a buffer with fewer than STEP_KEYS free slots its writer sets trig = s, on which the step's
+// end (topk_step_end, behind the step's barrier) cuts every buffer back to K <= cap - STEP_KEYS keys.  trig needs no atomic: every writer of
+// step s writes the same s, in front of the step's barrier; behind it every wave reads trig before it can write s + 1 -- or, if a fast wave does
+// write s + 1 first, then no one wrote s, and the slow wave reads a value that is not s either way.  If some one wrote s, all waves meet in
+// topk_compact's barriers before any goes on to step s + 1.  So trig == s is uniform over the workgroup.
+__device__ __forceinline__ void topk_append(uint64_t* buf, int cap, int32_t* cnt, int& trig, int ul, uint64_t key, int s) {
+    const int p = atomicAdd(&cnt[ul], 1);
+    buf[ul * cap + p] = key;
+    if (p >= cap - STEP_KEYS) trig = s;
+}
+
+// topk_compact for each of RS row sets.  (One set is written without the loop: through a loop of one trip the compiler computes what the calls
+// share in front of the sweep and every fp32 kernel holds one more VGPR across it.)
+template <int RS> __device__ __forceinline__ void topk_compact_sets(uint64_t* buf, int cap, int K, int32_t* cnt, uint64_t* thr_s) {
+    if constexpr (RS == 1) topk_compact(buf, cap, K, cnt, thr_s);
+    else
+        for (int rs = 0; rs < RS; ++rs) topk_compact(buf + rs * 16 * cap, cap, K, cnt + rs * 16, thr_s + rs * 16);
+}
+
+// Behind step s's barrier: on the trigger, compact each of the N / 4 row sets and reload this lane's thresholds (thr[rs * 4 + rr]: row rs * 16 + kg * 4 + rr).
+template <int N> __device__ __forceinline__ void topk_step_end(uint64_t* buf, int cap, int K, int32_t* cnt, uint64_t* thr_s, const int& trig, int s,
+                                                               int kg, uint64_t (&thr)[N]) {
+    if (trig != s) return;
+    topk_compact_sets<N / 4>(buf, cap, K, cnt, thr_s);
+#pragma unroll
+    for (int m = 0; m < N; ++m) thr[m] = thr_s[(m >> 2) * 16 + kg * 4 + (m & 3)];
+}
+
+// End of the workgroup's item range: the final compaction, then the K best keys of each of its rows u0 .. (sorted) go to the workspace.
+template <int RS> __device__ __forceinline__ void topk_write_out(uint64_t* buf, int cap, int K, int32_t* cnt, uint64_t* thr_s,
+                                                                 uint64_t* __restrict__ ws, int u0, int U) {
+    topk_compact_sets<RS>(buf, cap, K, cnt, thr_s);
+    for (int e = threadIdx.x; e < 16 * RS * K; e += 256) {
+        const int ul = e / K, j = e - ul * K;
+        if (u0 + ul < U) ws[((size_t)blockIdx.y * U + u0 + ul) * K + j] = buf[ul * cap + j];
+    }
+}
+
 // CAND (a4r_topk_items_cand, include/a4r_candidates.h): an item is kept only if cand[i] != 0 -- a byte per table row in global memory, tested
 // beside the exclusion search, for threshold-beating items only.  CAND = false is the kernel as it was and never reads cand.
 template <int E, bool CAND>
@@ -73,7 +123,8 @@ __global__ void __launch_bounds__(256) topk_partial_kernel(const float* __restri
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r16 = lane & 15, kg = lane >> 4;
     const int u0 = blockIdx.x * 16;
-    {   // 16 threads per user copy its exclusion ids, then put them in ascending order (rank of each id among the list, ties by position)
+    {   // 16 threads per user copy its exclusion ids and sort them: rank_sort_i32 (a4r_select.h) written out -- through it, or through a helper
+        // around this block, the kernel ran 0.5 % slower at K = 100 with equal registers (profiles/LOG.md)
         const int ul = tid >> 4, j0 = tid & 15, u = min(u0 + ul, U - 1);
         const int b = excl_ptr[u], n = max(0, min(excl_ptr[u + 1] - b, MAXX));
         for (int j = j0; j < n; j += 16) excl[ul][j] = excl_idx[b + j];
@@ -124,30 +175,20 @@ __global__ void __launch_bounds__(256) topk_partial_kernel(const float* __restri
                 if constexpr (CAND)
                     if (cand[i] == 0) continue;              // (ahead of the search: under a sparse mask the thresholds stay low for long)
                 const int ul = kg * 4 + rr;
-                int lo = 0, hi = nex[ul];
+                int lo = 0, hi = nex[ul];                    // sorted_has written out: through it another 0.5 % at K = 100 (profiles/LOG.md)
                 while (lo < hi) {
                     const int mid = (lo + hi) >> 1;
                     if (excl[ul][mid] < i) lo = mid + 1; else hi = mid;
                 }
                 if (!(lo < nex[ul] && excl[ul][lo] == i)) {
-                    const int p = atomicAdd(&cnt[ul], 1);
-                    buf[ul * cap + p] = key;
-                    if (p >= cap - STEP_KEYS) trig = s;      // (every writer of this step writes s; the next step's writers come after the barrier)
+                    topk_append(buf, cap, cnt, trig, ul, key, s);
                 }
             }
         }
         __syncthreads();
-        if (trig == s) {                                  // uniform: no wave can write step s + 1 before all have read it (see the note above)
-            topk_compact(buf, cap, K, cnt, thr_s);
-#pragma unroll
-            for (int rr = 0; rr < 4; ++rr) thr[rr] = thr_s[kg * 4 + rr];
-        }
+        topk_step_end(buf, cap, K, cnt, thr_s, trig, s, kg, thr);
     }
-    topk_compact(buf, cap, K, cnt, thr_s);
-    for (int e = tid; e < 16 * K; e += 256) {
-        const int ul = e / K, j = e - ul * K;
-        if (u0 + ul < U) ws[((size_t)blockIdx.y * U + u0 + ul) * K + j] = buf[ul * cap + j];
-    }
+    topk_write_out<1>(buf, cap, K, cnt, thr_s, ws, u0, U);
 }
 
 // Scores from the bf16 MFMA (a4r_topk_items_bf16, include/a4r_score_bf16.h): topk_partial_kernel at prec_b = bf16(prec), table_b = bf16(item_emb),
@@ -173,7 +214,7 @@ __global__ void __launch_bounds__(256) topk_partial_bf16_kernel(const bf16_t* __
     const int r16 = lane & 15, kg = lane >> 4;
     const int u0 = blockIdx.x * R;
     if (tid == 0) trig = -1;
-    for (int rs = 0; rs < RS; ++rs) {   // 16 threads per user copy its exclusion ids and put them in ascending order, one row set at a time (the sets' rows are disjoint)
+    for (int rs = 0; rs < RS; ++rs) {   // as in topk_partial_kernel, one row set at a time (the sets' rows are disjoint); written out for its reason: 0.4 - 0.6 % at K = 10
         const int ul = rs * 16 + (tid >> 4), j0 = tid & 15, u = min(u0 + ul, U - 1);
         const int b = excl_ptr[u], n = max(0, min(excl_ptr[u + 1] - b, MAXX));
         for (int j = j0; j < n; j += 16) excl[ul][j] = excl_idx[b + j];
@@ -205,12 +246,12 @@ __global__ void __launch_bounds__(256) topk_partial_bf16_kernel(const bf16_t* __
     __syncthreads();
     const SweepDeal<> deal(N1, wave);
     const int nsteps = deal.steps();                 // the 4 waves meet at every step's barrier
-    uint64_t thr[RS][4];
+    uint64_t thr[4 * RS];                            // [rs][rr]
     bool live[RS][4];
 #pragma unroll
     for (int rs = 0; rs < RS; ++rs)
 #pragma unroll
-        for (int rr = 0; rr < 4; ++rr) { thr[rs][rr] = 0; live[rs][rr] = u0 + rs * 16 + kg * 4 + rr < U; }
+        for (int rr = 0; rr < 4; ++rr) { thr[rs * 4 + rr] = 0; live[rs][rr] = u0 + rs * 16 + kg * 4 + rr < U; }
     uint4 bn[PD][KS];
 #pragma unroll
     for (int j = 0; j < PD; ++j) frag_load<E>(bn[j], table, deal.row(deal.first + j * deal.tstep, r16), kg);
@@ -231,7 +272,7 @@ __global__ void __launch_bounds__(256) topk_partial_bf16_kernel(const bf16_t* __
 #pragma unroll
                     for (int rr = 0; rr < 4; ++rr) {
                         const uint64_t key = topk_key(acc[rr], i);
-                        if (i < N1 && live[rs][rr] && key > thr[rs][rr]) {
+                        if (i < N1 && live[rs][rr] && key > thr[rs * 4 + rr]) {
                             if constexpr (CAND)
                                 if (cand[i] == 0) continue;
                             const int ul = rs * 16 + kg * 4 + rr;
@@ -241,29 +282,17 @@ __global__ void __launch_bounds__(256) topk_partial_bf16_kernel(const bf16_t* __
                                 if (excl[ul][mid] < i) lo = mid + 1; else hi = mid;
                             }
                             if (!(lo < nex[ul] && excl[ul][lo] == i)) {
-                                const int p = atomicAdd(&cnt[ul], 1);
-                                buf[(size_t)ul * cap + p] = key;
-                                if (p >= cap - STEP_KEYS) trig = s;      // (as in topk_partial_kernel)
+                                topk_append(buf, cap, cnt, trig, ul, key, s);
                             }
                         }
                     }
                 }
                 __syncthreads();
-                if (trig == s) {                          // uniform, as in topk_partial_kernel
-                    for (int rs = 0; rs < RS; ++rs) topk_compact(buf + (size_t)rs * 16 * cap, cap, K, cnt + rs * 16, thr_s + rs * 16);
-#pragma unroll
-                    for (int rs = 0; rs < RS; ++rs)
-#pragma unroll
-                        for (int rr = 0; rr < 4; ++rr) thr[rs][rr] = thr_s[rs * 16 + kg * 4 + rr];
-                }
+                topk_step_end(buf, cap, K, cnt, thr_s, trig, s, kg, thr);
             }
         }
     }
-    for (int rs = 0; rs < RS; ++rs) topk_compact(buf + (size_t)rs * 16 * cap, cap, K, cnt + rs * 16, thr_s + rs * 16);
-    for (int e = tid; e < R * K; e += 256) {
-        const int ul = e / K, j = e - ul * K;
-        if (u0 + ul < U) ws[((size_t)blockIdx.y * U + u0 + ul) * K + j] = buf[(size_t)ul * cap + j];
-    }
+    topk_write_out<RS>(buf, cap, K, cnt, thr_s, ws, u0, U);
 }
 
 // Similar items (a4r_topk_similar, include/a4r_similar.h): topk_partial_kernel with the 16 rows of a workgroup taken from the table itself.  The A
@@ -324,24 +353,13 @@ __global__ void __launch_bounds__(256) similar_partial_kernel(const float* __res
             if (col && qid[rr] != 0 && i != qid[rr] && sc >= min_sim && key > thr[rr]) {
                 if constexpr (CAND)
                     if (cand[i] == 0) continue;
-                const int ul = kg * 4 + rr;
-                const int p = atomicAdd(&cnt[ul], 1);
-                buf[ul * cap + p] = key;
-                if (p >= cap - STEP_KEYS) trig = s;          // (as in topk_partial_kernel)
+                topk_append(buf, cap, cnt, trig, kg * 4 + rr, key, s);
             }
         }
         __syncthreads();
-        if (trig == s) {
-            topk_compact(buf, cap, K, cnt, thr_s);
-#pragma unroll
-            for (int rr = 0; rr < 4; ++rr) thr[rr] = thr_s[kg * 4 + rr];
-        }
+        topk_step_end(buf, cap, K, cnt, thr_s, trig, s, kg, thr);
     }
-    topk_compact(buf, cap, K, cnt, thr_s);
-    for (int e = tid; e < 16 * K; e += 256) {
-        const int ul = e / K, j = e - ul * K;
-        if (u0 + ul < Q) ws[((size_t)blockIdx.y * Q + u0 + ul) * K + j] = buf[ul * cap + j];
-    }
+    topk_write_out<1>(buf, cap, K, cnt, thr_s, ws, u0, Q);
 }
 
 // a4r_row_inv_norms: 16 lanes per row; a lane squares and sums its 16-byte chunks j, j + 16, ... in fp64, then a butterfly over the row's lanes
@@ -399,8 +417,8 @@ __global__ void __launch_bounds__(256) topk_merge_kernel(const uint64_t* __restr
     }
 }
 
-int topk_ranges(int U, int N1) {                     // a4r_eval_rank's grid, at most MAX_RANGES item ranges
-    const int gy = sweep_ranges(U, N1);
+int topk_ranges(int U, int N1, int rs = 1) {         // a4r_eval_rank's grid over workgroups of 16 rs users, at most MAX_RANGES item ranges
+    const int gy = sweep_ranges((U + rs - 1) / rs, N1);
     return gy < MAX_RANGES ? gy : MAX_RANGES;
 }
 
@@ -412,13 +430,33 @@ int topk_cap(int K) {                                // candidate slots per user
 
 bool topk_shape_ok(int U, int N1, int K) { return U > 0 && N1 >= 2 && K >= 1 && K <= A4R_TOPK_MAX_K; }
 
-// the one launch path of both exports; cand is read by the CAND = true kernels only, the merge and decode launches are shared
+// What every export checks in front of its first HIP call: the pointers it requires (the optional ones, cand and inv_norm, are its own business)
+// and the workspace non-null, a shape and a width that are served, 16-byte operands a and b (b NULL: one operand), an 8-byte workspace.
+bool topk_args_ok(std::initializer_list<const void*> required, const void* a, const void* b, const void* ws, int rows, int N1, int E, int K) {
+    for (const void* p : required)
+        if (!p) return false;
+    return ws && topk_shape_ok(rows, N1, K) && width_served(WidthsF32{}, E) && aligned16(a, b) && (reinterpret_cast<uintptr_t>(ws) & 7u) == 0;
+}
+
+// The second launch of every export, behind its partial kernel: one item range is decoded, more are merged.  -> the launch status of both.
+int topk_finish(hipStream_t s, const uint64_t* ws, int32_t* ids, float* scores, int rows, int K, int gy) {
+    if (gy == 1) {
+        const int64_t n = (int64_t)rows * K;
+        const int blocks = (int)((n + 255) / 256 < 8192 ? (n + 255) / 256 : 8192);
+        hipLaunchKernelGGL(topk_decode_kernel, dim3(blocks), dim3(256), 0, s, ws, ids, scores, n);
+    } else {
+        const size_t mlds = (size_t)gy * K * sizeof(uint64_t);
+        if (int rc = a4r_set_lds(topk_merge_kernel, mlds)) return rc;
+        hipLaunchKernelGGL(topk_merge_kernel, dim3(rows), dim3(256), mlds, s, ws, ids, scores, rows, K, gy);
+    }
+    return a4r_launch_status();
+}
+
+// the one launch path of a4r_topk_items and a4r_topk_items_cand; cand is read by the CAND = true kernels only
 template <bool CAND>
 int topk_launch(void* stream, const float* prec, const float* item_emb, const int32_t* excl_ptr, const int32_t* excl_idx, const uint8_t* cand,
                 int32_t* ids, float* scores, void* ws, int U, int N1, int E, int K) {
-    if (!prec || !item_emb || !excl_ptr || !excl_idx || !ids || !scores || !ws || (CAND && !cand) || !topk_shape_ok(U, N1, K)) return A4R_EINVAL;
-    if (!width_served(WidthsF32{}, E) || !aligned16(prec, item_emb)) return A4R_EINVAL;
-    if (reinterpret_cast<uintptr_t>(ws) & 7u) return A4R_EINVAL;
+    if (!topk_args_ok({prec, item_emb, excl_ptr, excl_idx, ids, scores}, prec, item_emb, ws, U, N1, E, K) || (CAND && !cand)) return A4R_EINVAL;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     uint64_t* w = static_cast<uint64_t*>(ws);
     const int gy = topk_ranges(U, N1), cap = topk_cap(K);
@@ -430,17 +468,7 @@ int topk_launch(void* stream, const float* prec, const float* item_emb, const in
         if ((rc = a4r_set_lds(kernel, lds))) return;
         hipLaunchKernelGGL(kernel, grid, dim3(256), lds, s, prec, item_emb, excl_ptr, excl_idx, w, U, N1, K, cap, cand);
     });
-    if (rc) return rc;
-    if (gy == 1) {
-        const int64_t n = (int64_t)U * K;
-        const int blocks = (int)((n + 255) / 256 < 8192 ? (n + 255) / 256 : 8192);
-        hipLaunchKernelGGL(topk_decode_kernel, dim3(blocks), dim3(256), 0, s, w, ids, scores, n);
-    } else {
-        const size_t mlds = (size_t)gy * K * sizeof(uint64_t);
-        if ((rc = a4r_set_lds(topk_merge_kernel, mlds))) return rc;
-        hipLaunchKernelGGL(topk_merge_kernel, dim3(U), dim3(256), mlds, s, w, ids, scores, U, K, gy);
-    }
-    return a4r_launch_status();
+    return rc ? rc : topk_finish(s, w, ids, scores, U, K, gy);
 }
 
 // Row sets of a4r_topk_items_bf16 per (E, K).  LDS bounds them: a row set is a 16-user buffer of 16 cap keys (16 / 32 / 64 KB at K <= 64 / <= 192 / <= 256)
@@ -449,11 +477,6 @@ int topk_launch(void* stream, const float* prec, const float* item_emb, const in
 // the workgroups a CU holds and the launch ran twice as long; one at E = 512, where the A fragments of two sets are 128 VGPRs beside the tiles.
 int topk_bf16_rs(int E, int K) { return (K <= 64 && (E == 128 || E == 256)) ? 2 : 1; }
 template <int E> struct TopkBf16Shape { static constexpr int PD = E == 64 ? 4 : E == 128 ? 2 : 1; };      // tiles in flight per wave
-
-int topk_bf16_ranges(int U, int N1, int rs) {        // sweep_ranges over workgroups of 16 rs users, at most MAX_RANGES item ranges
-    const int gy = sweep_ranges((U + rs - 1) / rs, N1);
-    return gy < MAX_RANGES ? gy : MAX_RANGES;
-}
 
 template <int E, int RS, bool CAND>
 int topk_bf16_partial(hipStream_t s, const bf16_t* prec, const bf16_t* table, const int32_t* excl_ptr, const int32_t* excl_idx, const uint8_t* cand,
@@ -470,7 +493,7 @@ int topk_bf16_partial(hipStream_t s, const bf16_t* prec, const bf16_t* table, co
 template <bool CAND>
 int topk_bf16_launch(hipStream_t s, const bf16_t* prec, const bf16_t* table, const int32_t* excl_ptr, const int32_t* excl_idx, const uint8_t* cand,
                      int32_t* ids, float* scores, uint64_t* w, int U, int N1, int E, int K) {
-    const int rs = topk_bf16_rs(E, K), gy = topk_bf16_ranges(U, N1, rs);
+    const int rs = topk_bf16_rs(E, K), gy = topk_ranges(U, N1, rs);
     int rc = A4R_OK;
     with_width(WidthsF32{}, E, [&](auto e) {
         constexpr int W = decltype(e)::value;
@@ -479,17 +502,7 @@ int topk_bf16_launch(hipStream_t s, const bf16_t* prec, const bf16_t* table, con
         }
         rc = topk_bf16_partial<W, 1, CAND>(s, prec, table, excl_ptr, excl_idx, cand, w, U, N1, K, gy);
     });
-    if (rc) return rc;
-    if (gy == 1) {
-        const int64_t n = (int64_t)U * K;
-        const int blocks = (int)((n + 255) / 256 < 8192 ? (n + 255) / 256 : 8192);
-        hipLaunchKernelGGL(topk_decode_kernel, dim3(blocks), dim3(256), 0, s, w, ids, scores, n);
-    } else {
-        const size_t mlds = (size_t)gy * K * sizeof(uint64_t);
-        if ((rc = a4r_set_lds(topk_merge_kernel, mlds))) return rc;
-        hipLaunchKernelGGL(topk_merge_kernel, dim3(U), dim3(256), mlds, s, w, ids, scores, U, K, gy);
-    }
-    return a4r_launch_status();
+    return rc ? rc : topk_finish(s, w, ids, scores, U, K, gy);
 }
 
 // a4r_topk_similar's launches: the partial kernel above over top-K's grid with U = Q, then top-K's own decode or merge
@@ -505,17 +518,7 @@ int similar_launch(hipStream_t s, const float* item_emb, const float* inv, const
         if ((rc = a4r_set_lds(kernel, lds))) return;
         hipLaunchKernelGGL(kernel, grid, dim3(256), lds, s, item_emb, inv, query, cand, min_sim, w, Q, N1, K, cap);
     });
-    if (rc) return rc;
-    if (gy == 1) {
-        const int64_t n = (int64_t)Q * K;
-        const int blocks = (int)((n + 255) / 256 < 8192 ? (n + 255) / 256 : 8192);
-        hipLaunchKernelGGL(topk_decode_kernel, dim3(blocks), dim3(256), 0, s, w, ids, scores, n);
-    } else {
-        const size_t mlds = (size_t)gy * K * sizeof(uint64_t);
-        if ((rc = a4r_set_lds(topk_merge_kernel, mlds))) return rc;
-        hipLaunchKernelGGL(topk_merge_kernel, dim3(Q), dim3(256), mlds, s, w, ids, scores, Q, K, gy);
-    }
-    return a4r_launch_status();
+    return rc ? rc : topk_finish(s, w, ids, scores, Q, K, gy);
 }
 
 }  // namespace
@@ -531,9 +534,7 @@ extern "C" int a4r_row_inv_norms(void* stream, const float* table, float* inv, i
 
 extern "C" int a4r_topk_similar(void* stream, const float* item_emb, const float* inv_norm, const int32_t* query, const uint8_t* cand,
                                 float min_sim, int32_t* ids, float* scores, void* ws, int Q, int N1, int E, int K) {
-    if (!item_emb || !query || !ids || !scores || !ws || !topk_shape_ok(Q, N1, K) || min_sim != min_sim) return A4R_EINVAL;
-    if (!width_served(WidthsF32{}, E) || !aligned16(item_emb, nullptr)) return A4R_EINVAL;
-    if (reinterpret_cast<uintptr_t>(ws) & 7u) return A4R_EINVAL;
+    if (!topk_args_ok({item_emb, query, ids, scores}, item_emb, nullptr, ws, Q, N1, E, K) || min_sim != min_sim) return A4R_EINVAL;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     uint64_t* w = static_cast<uint64_t*>(ws);
     const auto launch = cand ? (inv_norm ? similar_launch<true, true> : similar_launch<true, false>)
@@ -548,14 +549,12 @@ extern "C" size_t a4r_topk_ws_bytes(int U, int N1, int K) {
 
 extern "C" size_t a4r_topk_bf16_ws_bytes(int U, int N1, int E, int K) {
     if (!topk_shape_ok(U, N1, K) || !width_served(WidthsF32{}, E)) return 0;
-    return (size_t)topk_bf16_ranges(U, N1, topk_bf16_rs(E, K)) * (size_t)U * (size_t)K * sizeof(uint64_t);
+    return (size_t)topk_ranges(U, N1, topk_bf16_rs(E, K)) * (size_t)U * (size_t)K * sizeof(uint64_t);
 }
 
 extern "C" int a4r_topk_items_bf16(void* stream, const void* prec_b, const void* table_b, const int32_t* excl_ptr, const int32_t* excl_idx,
                                    const uint8_t* cand, int32_t* ids, float* scores, void* ws, int U, int N1, int E, int K) {
-    if (!prec_b || !table_b || !excl_ptr || !excl_idx || !ids || !scores || !ws || !topk_shape_ok(U, N1, K)) return A4R_EINVAL;
-    if (!width_served(WidthsF32{}, E) || !aligned16(prec_b, table_b)) return A4R_EINVAL;
-    if (reinterpret_cast<uintptr_t>(ws) & 7u) return A4R_EINVAL;
+    if (!topk_args_ok({prec_b, table_b, excl_ptr, excl_idx, ids, scores}, prec_b, table_b, ws, U, N1, E, K)) return A4R_EINVAL;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const bf16_t* prec = static_cast<const bf16_t*>(prec_b);
     const bf16_t* table = static_cast<const bf16_t*>(table_b);

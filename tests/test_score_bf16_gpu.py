@@ -14,7 +14,7 @@ import torch
 
 import score_bf16_ref as SR
 from score_ce_bf16_ref import round_bf16
-from topk_ref import csr
+from topk_ref import csr, trigger_case, trigger_expected
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
@@ -125,6 +125,18 @@ def test_exact_on_integer_tables(K, E, N1, U, mode):
     np.testing.assert_array_equal(ids, ri)
     np.testing.assert_array_equal(sc.view(np.uint32), rs.view(np.uint32))
     np.testing.assert_array_equal(run_rank(prec_b, emb_b, target, lists, cand), rr)
+
+
+@pytest.mark.parametrize('K,E', [(64, 128), (256, 64)])              # two row sets at cap = 128; one row set with four tiles in flight per wave
+def test_exact_with_every_column_appended_at_every_step(K, E):
+    """topk_ref.trigger_case: the append, the trigger and the compaction at the bound of 64 keys per user and step"""
+    emb, prec, lists = trigger_case(E)
+    prec_b, emb_b = cast(prec), cast(emb)
+    assert torch.equal(emb_b.float().cpu(), torch.from_numpy(emb))   # integers up to 255 are bf16 numbers
+    ri, rs = trigger_expected(emb, prec, lists, K)
+    ids, sc = run_topk(prec_b, emb_b, [lists[u % 3] for u in range(prec.shape[0])], K)
+    np.testing.assert_array_equal(ids, ri)
+    np.testing.assert_array_equal(sc.view(np.uint32), rs.view(np.uint32))
 
 
 def test_empty_and_full_lists_for_every_user():

@@ -8,7 +8,7 @@ import pytest
 import torch
 
 import similar_ref as SR
-from topk_ref import csr
+from topk_ref import TRIGGER_N1, TRIGGER_U, csr, trigger_case
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
@@ -45,6 +45,19 @@ def test_similar_exact_dot_on_integer_tables(K, E, N1, Q):
     emb = SR.integer_table(rng, N1, E, zero_rows=query[::5] if N1 > 2 else ())    # an all-zero query: every score 0, the smallest ids
     emb = torch.from_numpy(emb).to(DEV)
     assert_exact(run_similar(emb, query, K, 'dot'), SR.similar_reference(emb, query, K, 'dot'))
+
+
+def test_similar_exact_dot_with_every_column_appended_at_every_step():
+    """topk_ref.trigger_case's table under the dot metric: a query from the top tile scores every item 255 x its tile (ascending with the tile: 64
+    appends per row and step, compaction at every step at K = 64), a query from tile 0 scores every item 0 (the order falls to the ids); query
+    ids 0 and N1 are dead rows.  32769 queries: one item range, a partial last workgroup."""
+    K, E = 64, 64
+    emb = torch.from_numpy(trigger_case(E)[0]).to(DEV)
+    kinds = np.concatenate([np.arange(TRIGGER_N1 - 16, TRIGGER_N1), np.arange(1, 17), [0, TRIGGER_N1]])
+    ri, rs = SR.similar_reference(emb, kinds, K, 'dot')              # once per distinct query
+    r = np.arange(TRIGGER_U) % kinds.size
+    got = run_similar(emb, kinds[r], K, 'dot')
+    assert_exact(got, (ri[r], rs[r]))
 
 
 COS_CASES = [(1, 64, 2, 1), (7, 512, 17, 15), (7, 64, 18, 17), (10, 64, 65, 16), (10, 512, 66, 16), (256, 512, 17, 16), (64, 512, 14720, 17),

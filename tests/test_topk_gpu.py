@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 import torch
 
-from topk_ref import csr, topk_reference
+from topk_ref import csr, topk_reference, trigger_case, trigger_expected
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
@@ -80,6 +80,16 @@ def test_topk_exact_on_integer_tables(K, E, N1, U):
     lists = excl_lists(rng, U, N1)
     ids, sc = run_topk(prec, emb, lists, K)
     ri, rs = oracle_exact(prec, emb, lists, K)
+    np.testing.assert_array_equal(ids, ri)
+    np.testing.assert_array_equal(sc.view(np.uint32), rs.view(np.uint32))
+
+
+@pytest.mark.parametrize('K,E', [(64, 64), (256, 64)])                # cap = 128: a step's 64 keys fill the buffer, compaction at every step; cap = 512
+def test_topk_exact_with_every_column_appended_at_every_step(K, E):
+    """topk_ref.trigger_case: the append, the trigger and the compaction at the bound of 64 keys per user and step"""
+    emb, prec, lists = trigger_case(E)
+    ri, rs = trigger_expected(emb, prec, lists, K)
+    ids, sc = run_topk(torch.from_numpy(prec).to(DEV), torch.from_numpy(emb).to(DEV), [lists[u % 3] for u in range(prec.shape[0])], K)
     np.testing.assert_array_equal(ids, ri)
     np.testing.assert_array_equal(sc.view(np.uint32), rs.view(np.uint32))
 

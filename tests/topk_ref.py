@@ -31,6 +31,39 @@ def topk_reference(scores, excl_lists, k):
     return ids, out
 
 
+TRIGGER_N1, TRIGGER_U = 4097, 32769
+
+
+def trigger_case(E):
+    """The input that drives the top-K kernels' append-and-trigger path at its bound (random tables raise the thresholds within a few tiles, after
+    which a step rarely adds a key).  Table: 256 tiles of 16 items, emb[i, 0] = the tile of item i, every other column 0 -- integers up to 255,
+    exact in bf16, every score exact in fp32.  32769 users: more than 2048 workgroups, so one item range, 64 steps of 4 tiles per workgroup, and
+    a partial last workgroup (or row set).  Three classes by u % 3, prec[u, 0] = 1 / -1 / 0: scores ascend with the tile, so all 64 lane columns
+    of every step beat the threshold (64 appends per user and step but for the excluded ids: at cap = 128 every step compacts) / scores descend,
+    nothing is appended after the first steps / every score ties and the order falls to the ids.  One exclusion list per class, each with ids of the
+    highest tiles; the first is full (264 ids) with repeats and ids outside the table.
+    -> (emb fp32 [N1, E], prec fp32 [U, E], the three lists)."""
+    N1, U = TRIGGER_N1, TRIGGER_U
+    emb = np.zeros((N1, E), np.float32)
+    emb[1:, 0] = (np.arange(1, N1) - 1) // 16
+    prec = np.zeros((U, E), np.float32)
+    prec[:, 0] = np.array([1.0, -1.0, 0.0], np.float32)[np.arange(U) % 3]
+    top = np.arange(N1 - 1, N1 - 401, -2)                          # every other id of the 25 highest tiles
+    lists = [np.concatenate([top, top[:60], [0, -3, N1, N1 + 7]]),
+             np.array([1, 2, 16, 17, 40, N1 - 1, N1 - 2, N1 - 16, N1 - 17, 0]),
+             np.array([N1 - 1, 3, 1, 5, 64, 65, N1 - 5, 3])]
+    assert len(lists[0]) == MAX_EXCL
+    return emb, prec, lists
+
+
+def trigger_expected(emb, prec, lists, k):
+    """The lists of trigger_case's users: one per class by topk_reference, broadcast -> (ids int64 [U, k], scores fp32 [U, k])"""
+    s = (prec[:3].astype(np.float64) @ emb.astype(np.float64).T).astype(np.float32)      # exact
+    ids, sc = topk_reference(s, lists, k)
+    cls = np.arange(prec.shape[0]) % 3
+    return ids[cls], sc[cls]
+
+
 def csr(lists):
     """-> (ptr int32 [U + 1], flat int32 [>= 1]) as a4r_topk_items reads an exclusion list."""
     lens = [len(x) for x in lists]
