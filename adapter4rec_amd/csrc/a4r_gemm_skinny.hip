@@ -215,6 +215,9 @@ int a4r_gemm_nt_skinnyk(hipStream_t s, const a4r_gemm_t& g) {
 int a4r_gemm_nt_skinny64(hipStream_t s, const a4r_gemm_t& g) {
     if (g.N != 64 || g.M % 64 || (g.K * 2) % 128 || g.in_dtype != A4R_BF16) return 1;
     if (g.bias && (reinterpret_cast<uintptr_t>(g.bias) & 3u)) return 1;
+    // the kernel requests Pre ahead of the K loop as elements of the output type: the one-byte derivative tensor (ldpre in bytes) was read at
+    // twice its offsets, past its end for the later rows -> the 128-tile kernel, which loads it byte-wise
+    if (g.dact == A4R_DACT_MULQ8_) return 1;
     const dim3 grid(g.M / 64), block(256);
     if (g.out_dtype == A4R_BF16)
         hipLaunchKernelGGL((skinny64_kernel<bf16_t, bf16_t>), grid, block, 0, s, g, a4r_thr16(g.drop_p), a4r_keep_scale(g.drop_p));

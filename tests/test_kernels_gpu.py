@@ -1486,8 +1486,10 @@ def test_unpack_add_and_scatter_fill():
 
 
 def test_gemm_tail_panels_split_launch():
-    """777 tiles on 256 CUs: the last 3 row panels are launched on the 128-tile kernel (a4r_gemm.hip); results and the dropout
-    mask (drop_row0) must equal the single-kernel launch."""
+    """777 tiles on 256 CUs.  Despite its name this is no split launch any more: gemm_tail_plan(66304, 768) == (256, 1), so the last 3 row
+    panels run as 32-row short tiles INSIDE the one 256-tile launch (a4r_gemm_rows_256 returns M; test_gemm_tail_plan_properties).  Results
+    and the dropout mask must equal the 128-tile kernel's (variant 1).  The split launch itself (split_rows, drop_row0), reachable only
+    under gemm_tail_max(0), is tested in tests/test_gemm_routes_gpu.py (route 'split')."""
     from adapter4rec_amd import _lib as L
     M, N, K = 259 * 256, 768, 2304
     A = rnd(M, K, dtype=torch.bfloat16, seed=71)
