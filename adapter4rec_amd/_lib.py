@@ -985,6 +985,8 @@ SATELLITES = {
     '_lib_similar': ('SIMILAR_SIGNATURES', ('row_inv_norms', 'topk_similar')),
     # evaluation and top-K with scores from the bf16 MFMA (--score_dtype bf16): include/a4r_score_bf16.h
     '_lib_score_bf16': ('SCORE_BF16_SIGNATURES', ('eval_rank_bf16', 'topk_items_bf16', 'topk_bf16_ws_bytes')),
+    # audience lists, every query item's best users of a user table: include/a4r_audience.h
+    '_lib_audience': ('AUDIENCE_SIGNATURES', ('topk_users',)),
 }
 
 

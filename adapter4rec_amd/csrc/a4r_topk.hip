@@ -19,6 +19,9 @@
 // Similar items (a4r_topk_similar, include/a4r_similar.h).  similar_partial_kernel is the same sweep and selection with the 16 rows of a workgroup
 // taken from the item table itself; compaction, merge and decode are the ones above, shared as they are.  a4r_row_inv_norms lives here too.
 //
+// Audience lists (a4r_topk_users, include/a4r_audience.h).  audience_partial_kernel is the similar kernel's row set swept over the user table: the
+// K best users of every query item, a user dropped when the item is in the user's own seen list (searched in global memory, no cap on its length).
+//
 // Where the pieces live.  The key, its decoding, the rank sort of an id list and the search of the sorted list: a4r_select.h, shared with the list
 // kernels.  Here, one copy each for the three partial kernels (fp32, bf16, similar), which keep their own loads and MFMA chains:
 // topk_append (with the trigger protocol), topk_step_end, topk_write_out and topk_compact; on the host topk_args_ok (every export's checks) and
@@ -362,6 +365,85 @@ __global__ void __launch_bounds__(256) similar_partial_kernel(const float* __res
     topk_write_out<1>(buf, cap, K, cnt, thr_s, ws, u0, Q);
 }
 
+// Audience lists (a4r_topk_users, include/a4r_audience.h): similar_partial_kernel's row set -- the A fragments straight from item_emb[query[..]] --
+// swept over the USER table, with the exclusion on the table side: row i is dropped for query q when q is in row i's own seen list
+// seen_idx[seen_ptr[i] .. seen_ptr[i + 1]).  The lists stay in global memory, whatever their length, and are read for threshold-beating keys only:
+// a lane whose column has such a key tests elig[i] (ELIG), loads the row's two offsets once for its four accumulator rows, and searches the list
+// for each beating row's query id.  lo and mid stay inside [b, e) whatever the list holds, so an unsorted list can mislist but never strays.
+// A row whose query id is no item is dead: it adds no key, its fragments are zero and no item_emb row is read for it.
+template <int E, bool ELIG>
+__global__ void __launch_bounds__(256) audience_partial_kernel(const float* __restrict__ item_emb, const int32_t* __restrict__ query,
+                                                               const float* __restrict__ user_vec, const int64_t* __restrict__ seen_ptr,
+                                                               const int32_t* __restrict__ seen_idx, const uint8_t* __restrict__ elig,
+                                                               uint64_t* __restrict__ ws, int Q, int N1, int U1, int K, int cap) {
+    constexpr int KS = E / 16;
+    extern __shared__ uint64_t buf[];                // [16][cap] candidate keys
+    __shared__ int32_t cnt[16];
+    __shared__ uint64_t thr_s[16];
+    __shared__ int trig;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int r16 = lane & 15, kg = lane >> 4;
+    const int u0 = blockIdx.x * 16;
+    if (tid < 16) { cnt[tid] = 0; thr_s[tid] = 0; }
+    if (tid == 0) trig = -1;
+    uint4 ua[KS];                                    // A operand: the 16 query items' rows
+    {
+        const int q = query[min(u0 + r16, Q - 1)];
+        if (q >= 1 && q < N1) frag_load<E>(ua, item_emb, q, kg);
+        else {
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) ua[ks] = make_uint4(0u, 0u, 0u, 0u);
+        }
+    }
+    int qid[4];                                      // the query ids of this lane's accumulator rows, 0 = dead
+#pragma unroll
+    for (int rr = 0; rr < 4; ++rr) {
+        const int r = u0 + kg * 4 + rr;
+        const int q = query[min(r, Q - 1)];
+        qid[rr] = (r < Q && q >= 1 && q < N1) ? q : 0;
+    }
+    __syncthreads();
+    const SweepDeal<> deal(U1, wave);
+    const int nsteps = deal.steps();                 // the 4 waves meet at every step's barrier
+    uint64_t thr[4] = {0, 0, 0, 0};
+    int t = deal.first;
+    uint4 bn[KS];
+    sweep_begin<E, true>(bn, user_vec, deal, r16, kg);
+    for (int s = 0; s < nsteps; ++s, t += deal.tstep) {
+        const int i = 1 + t * 16 + r16;                 // this lane's user row (>= U1 past the end of the table: nothing to add)
+        uint4 b[KS];
+        sweep_next<E, true>(b, bn, user_vec, deal, t, r16, kg);
+        const f32x4_t acc = score_tile<float>(ua, b);
+        uint64_t key[4];
+        bool any = false;
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) {
+            key[rr] = topk_key(acc[rr], i);
+            if (!(i < U1 && qid[rr] != 0 && key[rr] > thr[rr])) key[rr] = 0;      // (a live key is never 0)
+            any |= key[rr] != 0;
+        }
+        bool open = any;
+        if constexpr (ELIG)
+            if (any) open = elig[i] != 0;               // (ahead of the search: under a sparse mask the thresholds stay low for long)
+        if (open) {
+            const int64_t lb = seen_ptr[i], le = seen_ptr[i + 1];
+#pragma unroll
+            for (int rr = 0; rr < 4; ++rr) {
+                if (key[rr] == 0) continue;
+                int64_t lo = lb, hi = le;               // lo <= mid < hi <= le throughout: every read lies inside the row's own list
+                while (lo < hi) {
+                    const int64_t mid = lo + ((hi - lo) >> 1);
+                    if (seen_idx[mid] < qid[rr]) lo = mid + 1; else hi = mid;
+                }
+                if (!(lo < le && seen_idx[lo] == qid[rr])) topk_append(buf, cap, cnt, trig, kg * 4 + rr, key[rr], s);
+            }
+        }
+        __syncthreads();
+        topk_step_end(buf, cap, K, cnt, thr_s, trig, s, kg, thr);
+    }
+    topk_write_out<1>(buf, cap, K, cnt, thr_s, ws, u0, Q);
+}
+
 // a4r_row_inv_norms: 16 lanes per row; a lane squares and sums its 16-byte chunks j, j + 16, ... in fp64, then a butterfly over the row's lanes
 template <int E>
 __global__ void __launch_bounds__(256) row_inv_norms_kernel(const float* __restrict__ table, float* __restrict__ inv, int N1) {
@@ -521,7 +603,36 @@ int similar_launch(hipStream_t s, const float* item_emb, const float* inv, const
     return rc ? rc : topk_finish(s, w, ids, scores, Q, K, gy);
 }
 
+// a4r_topk_users' launches: the partial kernel above over top-K's grid with U = Q and the user table in the item table's place, then top-K's own
+// decode or merge
+template <bool ELIG>
+int audience_launch(hipStream_t s, const float* item_emb, const int32_t* query, const float* user_vec, const int64_t* seen_ptr,
+                    const int32_t* seen_idx, const uint8_t* elig, int32_t* rows, float* scores, uint64_t* w, int Q, int N1, int U1, int E, int K) {
+    const int gy = topk_ranges(Q, U1), cap = topk_cap(K);
+    const dim3 grid((Q + 15) / 16, gy);
+    const size_t lds = (size_t)16 * cap * sizeof(uint64_t);
+    int rc = A4R_OK;
+    with_width(WidthsF32{}, E, [&](auto e) {
+        const auto kernel = audience_partial_kernel<decltype(e)::value, ELIG>;
+        if ((rc = a4r_set_lds(kernel, lds))) return;
+        hipLaunchKernelGGL(kernel, grid, dim3(256), lds, s, item_emb, query, user_vec, seen_ptr, seen_idx, elig, w, Q, N1, U1, K, cap);
+    });
+    return rc ? rc : topk_finish(s, w, rows, scores, Q, K, gy);
+}
+
 }  // namespace
+
+extern "C" int a4r_topk_users(void* stream, const float* item_emb, const int32_t* query, const float* user_vec, const int64_t* seen_ptr,
+                              const int32_t* seen_idx, const uint8_t* elig, int32_t* rows, float* scores, void* ws, int Q, int N1, int U1, int E,
+                              int K) {
+    if (!topk_args_ok({item_emb, query, user_vec, seen_ptr, seen_idx, rows, scores}, item_emb, user_vec, ws, Q, U1, E, K) || N1 < 2 ||
+        (reinterpret_cast<uintptr_t>(seen_ptr) & 7u) != 0)
+        return A4R_EINVAL;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    uint64_t* w = static_cast<uint64_t*>(ws);
+    return elig ? audience_launch<true>(s, item_emb, query, user_vec, seen_ptr, seen_idx, elig, rows, scores, w, Q, N1, U1, E, K)
+                : audience_launch<false>(s, item_emb, query, user_vec, seen_ptr, seen_idx, nullptr, rows, scores, w, Q, N1, U1, E, K);
+}
 
 extern "C" int a4r_row_inv_norms(void* stream, const float* table, float* inv, int N1, int E) {
     if (!table || !inv || N1 < 1 || !width_served(WidthsF32{}, E) || !aligned16(table, nullptr)) return A4R_EINVAL;

@@ -23,7 +23,7 @@ from ..inject import freeze_all
 from ..optim import from_args as optimizer_from_args
 from . import Model, ModelCPC, ViTForImageClassification, ViTMAEModel
 from .data_utils import eval_model, get_itemId_embeddings, get_itemLMDB_embeddings, open_image_db, read_behaviors, read_images
-from ..data_utils.eval_flags import check_flags, eval_restriction, write_recommend_mode, write_similar_mode
+from ..data_utils.eval_flags import check_flags, eval_restriction, write_audience_mode, write_recommend_mode, write_similar_mode
 from .image_io import Build_Lmdb_Dataset, assemble_batch, collate_host
 from .inject import inject_adapters, optimizer_groups
 from .parameters import parse_args
@@ -250,7 +250,8 @@ def test(args, use_modal, local_rank, Log_file, Log_screen, model_dir, start_tim
 def recommend(args, use_modal, local_rank, Log_file, Log_screen, model_dir, start_time):
     """--mode recommend: the model test() evaluates, asked for the --topk next items after every kept user's whole known sequence (the test
     split's input with its held-out item), everything in that sequence excluded; rank 0 writes --recommend_out.
-    --mode similar: the same checkpoint and item table, asked for every item's --topk nearest items instead; rank 0 writes --similar_out."""
+    --mode similar: the same checkpoint and item table, asked for every item's --topk nearest items instead; rank 0 writes --similar_out.
+    --mode audience: the same checkpoint, table and users, asked for every item's --topk best users instead; rank 0 writes --audience_out."""
     if not use_modal:
         check_id_flags(args)
     cv_model = load_backbone(args, Log_file) if use_modal else None
@@ -266,6 +267,9 @@ def recommend(args, use_modal, local_rank, Log_file, Log_screen, model_dir, star
         emb = get_itemLMDB_embeddings(model, item_num, item_id_to_keys, 256, args, local_rank, db=db)
     if args.mode == 'similar':                                         # the same table, asked for every item's nearest items: no user is encoded
         write_similar_mode(args, emb, 256, path, before_name2id, model_dir, Log_file)
+        return
+    if args.mode == 'audience':                                        # the same users and table with the roles swapped: every item's best users
+        write_audience_mode(args, model, users_test, hist_test, emb, 256, path, before_name2id, model_dir, Log_file)
         return
     write_recommend_mode(args, model, users_test, hist_test, emb, 256, path, before_name2id, model_dir, Log_file)
 
@@ -289,7 +293,7 @@ def main(argv=None):
     Log_file.info(args)
     os.makedirs(model_dir, exist_ok=True)
     t0 = time.time()
-    if args.mode in ('recommend', 'similar'):
+    if args.mode in ('recommend', 'similar', 'audience'):
         recommend(args, use_modal, local_rank, Log_file, Log_screen, model_dir, t0)
     else:
         (test if 'test' in args.mode else train)(args, use_modal, local_rank, Log_file, Log_screen, model_dir, t0)

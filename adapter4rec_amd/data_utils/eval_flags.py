@@ -1,6 +1,7 @@
 """The flags that restrict or re-rank what evaluation and recommendation range over (--topk .. --eval_negatives_out) and those of --mode similar
-(--similar_*), for both entry points (run.py, cv/run_adapter.py): their declaration, their refusals, and their translation into the arguments of
-data_utils.metrics (eval_model's restriction, write_recommendations' and write_similar_items' calls).  No kernel is called from here."""
+(--similar_*) and --mode audience (--audience_*), for both entry points (run.py, cv/run_adapter.py): their declaration, their refusals, and their
+translation into the arguments of data_utils.metrics (eval_model's restriction, write_recommendations', write_similar_items' and write_audience's
+calls).  No kernel is called from here."""
 import math
 import os
 
@@ -9,7 +10,7 @@ import torch.distributed as dist
 from .._lib_diversify import MMR_MAX_POOL
 from .._lib_user_lists import LIST_MAX
 from .metrics import (SCORE_DTYPES, SIMILAR_METRICS, Diversify, EvalNegatives, candidate_mask, item_counts, read_candidate_lists, read_candidates,
-                      read_similar_items, write_eval_negatives, write_recommendations, write_similar_items)
+                      read_audience_users, read_similar_items, write_audience, write_eval_negatives, write_recommendations, write_similar_items)
 from .preprocess import read_behavior_names
 
 
@@ -29,6 +30,9 @@ def add_eval_flags(p):
     p.add_argument('--similar_items', type=str, default=None)          # --mode similar: a file of item names, one per line -- the query items, in file order (default: every item)
     p.add_argument('--similar_metric', type=str, default='cos', choices=list(SIMILAR_METRICS))      # --mode similar: cosine, or the dot product --mode recommend ranks by
     p.add_argument('--similar_min', type=float, default=None)          # --mode similar: list only the items scoring at least this (0.95 under cos: near-duplicates)
+    p.add_argument('--audience_out', type=str, default=None)           # --mode audience: output file (default <model_dir>/audience_<load_ckpt_name>.tsv)
+    p.add_argument('--audience_items', type=str, default=None)         # --mode audience: a file of item names, one per line -- the query items, in file order (default: every item)
+    p.add_argument('--audience_users', type=str, default=None)         # --mode audience: a file of user names, one per line -- the eligible users (default: every user)
     p.add_argument('--score_dtype', type=str, default='fp32', choices=list(SCORE_DTYPES))      # --mode test / recommend and the per-epoch evaluation: bf16 = score against the item table on the bf16 MFMA (operands rounded, fp32 sums)
 
 
@@ -38,6 +42,7 @@ def check_flags(args):
     check_eval_negatives_flag(args)
     check_diversify_flag(args)
     check_similar_flag(args)
+    check_audience_flag(args)
     check_score_dtype_flag(args)
 
 
@@ -49,6 +54,8 @@ def check_score_dtype_flag(args):
         return
     if args.mode == 'similar':
         raise ValueError('--score_dtype bf16 is not honoured by --mode similar: a4r_topk_similar scores in fp32 only')
+    if args.mode == 'audience':
+        raise ValueError('--score_dtype bf16 is not honoured by --mode audience: a4r_topk_users scores in fp32 only')
     if getattr(args, 'candidate_lists', None):
         raise ValueError('--score_dtype bf16 and --candidate_lists cannot be combined: the kernels of a user\'s own list score in fp32 only')
     if int(getattr(args, 'eval_negatives', 0) or 0) != 0:
@@ -83,6 +90,25 @@ def check_similar_flag(args):
         raise ValueError('--eval_negatives is an evaluation protocol: it is not honoured by --mode similar')
     if args.similar_min is not None and math.isnan(float(args.similar_min)):
         raise ValueError('--similar_min nan: not a number')
+
+
+def check_audience_flag(args):
+    """--mode audience lists users for items: the flags that restrict, re-rank or evaluate the lists of users' items and those of --mode similar
+    are refused under it instead of ignored (--candidate_items / --candidate_lists: check_candidate_flag; --score_dtype bf16:
+    check_score_dtype_flag), and --audience_out / --audience_items /
+    --audience_users are refused under every other mode."""
+    if args.mode != 'audience':
+        for flag in ('audience_out', 'audience_items', 'audience_users'):
+            if getattr(args, flag, None) is not None:
+                raise ValueError(f'--{flag} is honoured by --mode audience only, not by --mode {args.mode}')
+        return
+    if getattr(args, 'diversify', 'none') != 'none':
+        raise ValueError(f'--diversify {args.diversify} re-ranks the lists of users: it is not honoured by --mode audience')
+    if int(getattr(args, 'eval_negatives', 0) or 0) != 0 or getattr(args, 'eval_negatives_out', None):
+        raise ValueError('--eval_negatives is an evaluation protocol: it is not honoured by --mode audience')
+    for flag, default in (('eval_neg_sampling', 'uniform'), ('eval_neg_seed', 20240607)):
+        if getattr(args, flag, default) != default:
+            raise ValueError(f'--{flag} belongs to --eval_negatives, an evaluation protocol: it is not honoured by --mode audience')
 
 
 def check_candidate_flag(args):
@@ -221,3 +247,23 @@ def write_similar_mode(args, item_embeddings, batch_size, behaviors_path, name2i
         Log_file.info(f'similar items: {query.size} of {len(item_names) - 1} from {args.similar_items}')
     write_similar_items(item_embeddings, args.topk, batch_size, item_names, similar_out_path(args, model_dir), item_ids=query, candidates=mask,
                         metric=args.similar_metric, min_sim=args.similar_min, Log_file=Log_file)
+
+
+def audience_out_path(args, model_dir):
+    return args.audience_out or os.path.join(model_dir, f'audience_{args.load_ckpt_name}.tsv')
+
+
+def write_audience_mode(args, model, users_test, hist_test, item_embeddings, batch_size, behaviors_path, name2id, model_dir, Log_file):
+    """The tail of --mode audience in both entry points: the --topk best users of every item (or of --audience_items' items, in file order) among
+    every user (or --audience_users' users), a user never listed for an item of the user's known sequence, written by rank 0 to --audience_out
+    under the names of the behaviours file."""
+    user_names, item_names = read_behavior_names(behaviors_path, name2id, args.max_seq_len, args.min_seq_len)
+    query = eligible = None
+    if getattr(args, 'audience_items', None):
+        query = read_similar_items(args.audience_items, item_names)
+        Log_file.info(f'audience items: {query.size} of {len(item_names) - 1} from {args.audience_items}')
+    if getattr(args, 'audience_users', None):
+        eligible = read_audience_users(args.audience_users, user_names)
+        Log_file.info(f'audience users: {int(eligible.sum())} of {len(user_names)} from {args.audience_users}')
+    write_audience(model, users_test, hist_test, item_embeddings, args.topk, batch_size, args, user_names, item_names,
+                   audience_out_path(args, model_dir), item_ids=query, eligible=eligible, Log_file=Log_file)

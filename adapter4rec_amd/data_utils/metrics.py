@@ -556,17 +556,32 @@ def _means_over_valid(ranks, valid, n_users, topK, world, Log_file, v_or_t, labe
     return mean_eval[0]
 
 
-def _recommend_inputs(user_seqs, exclude, uids, T):
-    """recommend()'s host side for the listed users: each one's last T items left-padded into ids / log_mask [n, T] (the layout _prepare_eval_set
-    gives an evaluation input), and the exclusion lists as CSR (ptr [n + 1] int64, flat ids int32 + one spare 0)."""
+def _user_inputs(user_seqs, uids, T):
+    """The user tower's input for the listed users: each one's last T items left-padded into ids / log_mask [n, T] (the layout _prepare_eval_set
+    gives an evaluation input).  recommend and user_vectors build their inputs here."""
     import itertools
     seqs = [list(user_seqs[int(u)])[-T:] for u in uids]
     n = len(seqs)
     lens = np.fromiter((len(s) for s in seqs), dtype=np.int64, count=n)
     if n and int(lens.min()) == 0:
         raise ValueError(f'user {int(uids[int(lens.argmin())])}: an empty sequence has nothing to recommend from')
-    ids, mask = _left_pad(np.fromiter(itertools.chain.from_iterable(seqs), dtype=np.int64, count=int(lens.sum())), lens, T)
-    ex = [np.asarray(exclude[int(u)]).reshape(-1).astype(np.int64) for u in uids] if exclude is not None else [np.asarray(user_seqs[int(u)], dtype=np.int64).reshape(-1) for u in uids]
+    return _left_pad(np.fromiter(itertools.chain.from_iterable(seqs), dtype=np.int64, count=int(lens.sum())), lens, T)
+
+
+def _encode_users(inner, emb, ids_np, mask_np, a, b):
+    """The user vectors of rows a .. b of _user_inputs' arrays: their items' rows of ``emb`` through user_encoder, last position -> fp32 [b - a, E]."""
+    dev = emb.device
+    x = torch.from_numpy(ids_np[a:b]).to(dev)
+    input_embs = emb[x.reshape(-1)].view(b - a, ids_np.shape[1], emb.shape[1])
+    return inner.user_encoder(input_embs, torch.from_numpy(mask_np[a:b]).to(dev), None)[:, -1].contiguous()
+
+
+def _recommend_inputs(user_seqs, exclude, uids, T):
+    """recommend()'s host side for the listed users: _user_inputs' ids / log_mask [n, T], and the exclusion lists as CSR (ptr [n + 1] int64,
+    flat ids int32 + one spare 0)."""
+    ids, mask = _user_inputs(user_seqs, uids, T)
+    n = len(uids)
+    ex =[np.asarray(exclude[int(u)]).reshape(-1).astype(np.int64) for u in uids] if exclude is not None else [np.asarray(user_seqs[int(u)], dtype=np.int64).reshape(-1) for u in uids]
     ptr, flat, el = _csr_int32(ex)
     if n and int(el.max()) > L.EVAL_MAX_HISTORY:              # never truncate: an unexcluded item would be recommended silently
         u = int(el.argmax())
@@ -608,7 +623,6 @@ def _recommend(model, user_seqs, item_embeddings, k, args, exclude, user_ids, ca
     dev = next(model.parameters()).device
     emb = item_embeddings.to(dev).float().contiguous()
     T = int(args.max_seq_len)
-    E = emb.shape[1]
     k = int(k)
     cand = candidate_mask(candidates, emb.shape[0], dev)
     uids = np.arange(len(user_seqs), dtype=np.int64) if user_ids is None else np.asarray(user_ids, dtype=np.int64).reshape(-1)
@@ -630,9 +644,7 @@ def _recommend(model, user_seqs, item_embeddings, k, args, exclude, user_ids, ca
         for a in range(0, uids.size, step):
             b = min(a + step, uids.size)
             nb = b - a
-            x = torch.from_numpy(ids_np[a:b]).to(dev)
-            input_embs = emb[x.reshape(-1)].view(nb, T, E)
-            prec = inner.user_encoder(input_embs, torch.from_numpy(mask_np[a:b]).to(dev), None)[:, -1].contiguous()
+            prec = _encode_users(inner, emb, ids_np, mask_np, a, b)
             h0, h1 = int(ptr_np[a]), int(ptr_np[b])
             ptr = torch.from_numpy((ptr_np[a:b + 1] - h0).astype(np.int32)).to(dev)
             ids = torch.empty(nb, kk, dtype=torch.int32, device=dev)
@@ -798,4 +810,168 @@ def write_similar_items(item_embeddings, k, batch_size, item_names, path, item_i
     if Log_file is not None:
         best = float(scores[has, 0].astype(np.float64).mean()) if has.any() else 0.0
         Log_file.info('similar   top-{} lists of {} items, {} with a neighbour, mean best score {:0.5f} -> {}'.format(k, nq, int(has.sum()), best, path))
+    return path
+
+
+def user_vectors(model, user_seqs, item_embeddings, args, user_ids=None):
+    """The user tower's vector of each listed user (default: every user of ``user_seqs``) -> fp32 [n, E] on the model's device: the last
+    ``max_seq_len`` items of ``user_seqs[u]`` through ``user_encoder``, last position, in batches of A4R_EVAL_USER_BATCH (default 8192) -- the
+    vectors recommend() scores the item table with (the same inputs, built by the same code)."""
+    inner = _inner(model, args)
+    dev = next(model.parameters()).device
+    emb = item_embeddings.to(dev).float().contiguous()
+    uids = np.arange(len(user_seqs), dtype=np.int64) if user_ids is None else np.asarray(user_ids, dtype=np.int64).reshape(-1)
+    if uids.size == 0:
+        return torch.zeros(0, emb.shape[1], dtype=torch.float32, device=dev)
+    ids_np, mask_np = _user_inputs(user_seqs, uids, int(args.max_seq_len))
+    step = int(os.environ.get('A4R_EVAL_USER_BATCH', 0)) or 8192          # (eval_ranks' user batch)
+    out = []
+    model.eval()
+    with torch.no_grad():
+        for a in range(0, uids.size, step):
+            out.append(_encode_users(inner, emb, ids_np, mask_np, a, min(a + step, uids.size)).float())
+    return torch.cat(out)
+
+
+def read_audience_users(path, user_names):
+    """An --audience_users file -> bool array [n_users]: one user name per line, the names --mode recommend writes (``user_names[u]``:
+    preprocess.read_behavior_names).  Blank lines and repeats are ignored; names that are no user raise ValueError listing the first few, as
+    read_candidates does; a file without any name raises as well."""
+    index = {name: u for u, name in enumerate(user_names) if name is not None}
+    mask = np.zeros(len(user_names), dtype=bool)
+    unknown = []
+    with open(path) as f:
+        for line in f:
+            name = line.strip()
+            if not name:
+                continue
+            u = index.get(name)
+            if u is None:
+                if name not in unknown:
+                    unknown.append(name)
+            else:
+                mask[u] = True
+    if unknown:
+        raise ValueError(f'{path}: {len(unknown)} name(s) that are no user of this dataset: ' + ', '.join(unknown[:5]) + (' ...' if len(unknown) > 5 else ''))
+    if not mask.any():
+        raise ValueError(f'{path}: no user name in the file')
+    return mask
+
+
+def audience_seen_csr(seen, n_users):
+    """The users' seen lists as a4r_topk_users reads them: ``seen[u]`` (any iterable of item ids, u = 0 .. n_users - 1) -> (ptr int64
+    [n_users + 2], flat int32): row 0 -- the pad row of the user table -- is empty, row u + 1 holds user u's ids ascending, each once.  There is
+    no cap on a list's length.  An id below 0 or beyond int32 names no item and becomes -1 (harmless, like any id outside 1 .. N)."""
+    rows = [np.zeros(0, np.int64)]
+    for u in range(n_users):
+        x = np.asarray(seen[u], dtype=np.int64).reshape(-1)
+        rows.append(np.unique(np.where((x < 0) | (x > np.iinfo(np.int32).max), -1, x)))
+    lens = np.fromiter((x.size for x in rows), dtype=np.int64, count=len(rows))
+    ptr = np.zeros(len(rows) + 1, dtype=np.int64)
+    np.cumsum(lens, out=ptr[1:])
+    return ptr, np.concatenate(rows).astype(np.int32)
+
+
+def _eligible_rows(eligible, n_users, dev):
+    """``eligible`` (bool [n_users], tensor or array, or None) -> (uint8 [n_users + 1] on ``dev`` with the pad row 0 not eligible, or None; the
+    number of eligible users)."""
+    if eligible is None:
+        return None, n_users
+    m = np.asarray(eligible.cpu() if isinstance(eligible, torch.Tensor) else eligible)
+    if m.ndim != 1 or m.shape[0] != n_users:
+        raise ValueError(f'eligible: one entry per user expected, [{n_users}], got {tuple(m.shape)}')
+    m = m != 0
+    return torch.from_numpy(np.concatenate([np.zeros(1, bool), m]).astype(np.uint8)).to(dev), int(m.sum())
+
+
+def _audience(table, emb, k, q, ptr, flat, elig):
+    """audience's launches on a user table that stands (fp32 [n_users + 1, E], row 0 zero): the query items ``q`` (int64 array) in batches of
+    A4R_EVAL_USER_BATCH, one a4r_topk_users launch pair each -> (user ids LongTensor [Q, k] = row - 1, a pad -1; scores fp32 [Q, k])."""
+    dev = table.device
+    if q.size == 0:
+        return torch.zeros(0, k, dtype=torch.long, device=dev), torch.zeros(0, k, dtype=torch.float32, device=dev)
+    q32 = torch.from_numpy(np.where((q < 0) | (q > np.iinfo(np.int32).max), 0, q).astype(np.int32)).to(dev)      # (an id outside int32 names no row: a pad list)
+    step = int(os.environ.get('A4R_EVAL_USER_BATCH', 0)) or 8192          # (eval_ranks' user batch)
+    out_rows, out_scores = [], []
+    for a in range(0, q.size, step):
+        b = min(a + step, q.size)
+        rows = torch.empty(b - a, k, dtype=torch.int32, device=dev)
+        scores = torch.empty(b - a, k, dtype=torch.float32, device=dev)
+        L.topk_users(emb, q32[a:b], table, ptr, flat, elig, k, rows, scores)
+        out_rows.append(rows.long() - 1)
+        out_scores.append(scores)
+    return torch.cat(out_rows), torch.cat(out_scores)
+
+
+def _user_table(vectors):
+    """user vectors [n, E] -> the table a4r_topk_users sweeps: [n + 1, E] with a zero pad row 0, user u in row u + 1"""
+    return torch.cat([torch.zeros(1, vectors.shape[1], dtype=torch.float32, device=vectors.device), vectors.float()]).contiguous()
+
+
+def audience(model, user_seqs, item_embeddings, k, args, item_ids=None, seen=None, eligible=None):
+    """The k best users for each query item: whom to show the item to -- a new or cold item (the item tower gives it a vector from its content
+    alone), a campaign, the seed users of an item nobody has interacted with.
+
+    ``user_seqs[u]``: the users' item ids, as recommend's; every user is encoded (user_vectors) into one table per call.  ``item_ids`` (default:
+    1 .. N): the query items, in the order of the returned rows; an id outside 1 .. N gets pad slots only, a repeated id an equal row.
+    ``seen[u]`` (default: ``user_seqs[u]``): the items user u has seen -- a user is never listed for an item in it; of any length (sorted and
+    de-duplicated here, audience_seen_csr: the 264-id cap of recommend's exclusion lists does not apply).  ``eligible`` (bool [n_users], or
+    None): only these users are listed.
+    Returns (user ids LongTensor [Q, k], scores fp32 [Q, k]) on the model's device: score descending, ties by smaller user id; fewer than k
+    users: id -1 / score -inf in the remaining slots.  score(item, user) has the bits recommend() gives the same pair.  The rule:
+    include/a4r_audience.h.  One a4r_topk_users launch pair per batch of A4R_EVAL_USER_BATCH (default 8192) query items; the [items, users]
+    score matrix is never formed."""
+    k = int(k)
+    dev = next(model.parameters()).device
+    emb = item_embeddings.to(dev).float().contiguous()
+    n_users = len(user_seqs)
+    q = np.arange(1, emb.shape[0], dtype=np.int64) if item_ids is None else np.asarray(torch.as_tensor(item_ids).cpu(), dtype=np.int64).reshape(-1)
+    elig, _ = _eligible_rows(eligible, n_users, dev)
+    ptr, flat = audience_seen_csr(user_seqs if seen is None else seen, n_users)
+    table = _user_table(user_vectors(model, user_seqs, emb, args))
+    return _audience(table, emb, k, q, torch.from_numpy(ptr).to(dev), torch.from_numpy(flat).to(dev), elig)
+
+
+def write_audience(model, user_seqs, user_history, item_embeddings, k, batch_size, args, user_names, item_names, path, item_ids=None, eligible=None,
+                   Log_file=None):
+    """The runners' --mode audience: the k best users of the query items ``item_ids`` (default: every item 1 .. N) among ``eligible`` (bool
+    [n_users], default: every user), a user never listed for an item of ``user_history[u]`` or the last item of ``user_seqs[u]`` -- everything
+    the user is known to have seen: write_recommendations' exclusion, without its 264-id cap.  The users are sharded over the data-parallel
+    ranks for the user tower and their vectors gathered as get_item_embeddings gathers its shards; the query items are sharded as
+    write_similar_items shards them.  Rank 0 writes ``path``: one line per query item that has at least one user, in query order,
+    ``item_name \\t user_1 ... user_k \\t score_1 ... score_k`` (pad slots omitted, scores as %.9g).  ``Log_file`` gets one line, ``audience``.
+    Returns the path on rank 0, None elsewhere."""
+    k = int(k)
+    dev = next(model.parameters()).device
+    emb = item_embeddings.to(dev).float().contiguous()
+    n_users = len(user_seqs)
+    q = np.arange(1, emb.shape[0], dtype=np.int64) if item_ids is None else np.asarray(item_ids, dtype=np.int64).reshape(-1)
+    nq = int(q.size)
+    if nq == 0:
+        raise ValueError('write_audience: no query item')
+    if n_users == 0:
+        raise ValueError('write_audience: no user')
+    elig, n_elig = _eligible_rows(eligible, n_users, dev)
+    lo, hi, chunk, world = _my_shard(n_users)
+    table = _user_table(_gather_shards(user_vectors(model, user_seqs, emb, args, np.arange(lo, hi, dtype=np.int64)), n_users, chunk, world))
+    seen = [np.concatenate([np.asarray(user_history[u], dtype=np.int64).reshape(-1), np.asarray(user_seqs[u][-1:], dtype=np.int64)]) for u in range(n_users)]
+    ptr, flat = audience_seen_csr(seen, n_users)
+    world, rank_id, rows = _shard_users(nq, batch_size)
+    ids, scores = _audience(table, emb, k, q[np.asarray(rows, dtype=np.int64)], torch.from_numpy(ptr).to(dev), torch.from_numpy(flat).to(dev), elig)
+    ids, scores = _gather_cat(ids, world), _gather_cat(scores, world)
+    if rank_id != 0:
+        return None
+    ids, scores = ids[:nq].cpu().numpy(), scores[:nq].cpu().numpy()
+    has = ids[:, 0] >= 0
+    with open(path, 'w') as f:
+        for r in range(nq):
+            if not has[r]:
+                continue
+            keep = ids[r] >= 0
+            f.write(item_names[int(q[r])] + '\t' + ' '.join(user_names[int(u)] for u in ids[r][keep]) + '\t'
+                    + ' '.join('%.9g' % float(s) for s in scores[r][keep]) + '\n')
+    if Log_file is not None:
+        best = float(scores[has, 0].astype(np.float64).mean()) if has.any() else 0.0
+        Log_file.info('audience   top-{} lists of {} items over {} users ({} eligible), {} with a user, mean best score {:0.5f} -> {}'.format(
+            k, nq, n_users, n_elig, int(has.sum()), best, path))
     return path

@@ -10,7 +10,7 @@ from .data_utils.eval_flags import add_eval_flags
 def build_parser():
     p = argparse.ArgumentParser()
     # ============== data_dir ==============
-    p.add_argument('--mode', type=str, default='train', choices=['train', 'test', 'load', 'recommend', 'similar'])
+    p.add_argument('--mode', type=str, default='train', choices=['train', 'test', 'load', 'recommend', 'similar', 'audience'])
     p.add_argument('--item_tower', type=str, default='modal', choices=['modal', 'id'])
     p.add_argument('--root_data_dir', type=str, default='../')
     p.add_argument('--dataset', type=str, default='Adressa')

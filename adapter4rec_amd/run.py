@@ -18,7 +18,7 @@ from torch.utils.data import DataLoader
 
 from .data_utils import (BuildTrainDataset, eval_model, get_doc_input_bert, get_item_embeddings, read_behaviors,
                          read_news_bert)
-from .data_utils.eval_flags import check_flags, eval_restriction, write_recommend_mode, write_similar_mode
+from .data_utils.eval_flags import check_flags, eval_restriction, write_audience_mode, write_recommend_mode, write_similar_mode
 from .data_utils.dataset import DeviceTrainSampler
 from .data_utils.utils import (get_checkpoint, para_and_log, report_time_eval, report_time_train, save_model, setuplogger)
 from .ddp import FlatDDP, any_rank
@@ -207,7 +207,8 @@ def test(args, use_modal, local_rank, Log_file, Log_screen, model_dir, start_tim
 def recommend(args, use_modal, local_rank, Log_file, Log_screen, model_dir, start_time):
     """--mode recommend: the model test() evaluates, asked for the --topk next items after every kept user's whole known sequence (the test
     split's input with its held-out item), everything in that sequence excluded; rank 0 writes --recommend_out.
-    --mode similar: the same checkpoint and item table, asked for every item's --topk nearest items instead; rank 0 writes --similar_out."""
+    --mode similar: the same checkpoint and item table, asked for every item's --topk nearest items instead; rank 0 writes --similar_out.
+    --mode audience: the same checkpoint, table and users, asked for every item's --topk best users instead; rank 0 writes --audience_out."""
     tokenizer, bert_model = load_backbone(args, Log_file)
     path = os.path.join(args.root_data_dir, args.dataset, args.behaviors)
     before_id2dic, before_name2id = read_news_bert(os.path.join(args.root_data_dir, args.dataset, args.news), args, tokenizer)
@@ -218,6 +219,9 @@ def recommend(args, use_modal, local_rank, Log_file, Log_screen, model_dir, star
     emb = get_item_embeddings(model, item_content, 512, args, use_modal, local_rank)
     if args.mode == 'similar':                                         # the same table, asked for every item's nearest items: no user is encoded
         write_similar_mode(args, emb, 512, path, before_name2id, model_dir, Log_file)
+        return
+    if args.mode == 'audience':                                        # the same users and table with the roles swapped: every item's best users
+        write_audience_mode(args, model, users_test, hist_test, emb, 512, path, before_name2id, model_dir, Log_file)
         return
     write_recommend_mode(args, model, users_test, hist_test, emb, 512, path, before_name2id, model_dir, Log_file)
 
@@ -246,7 +250,7 @@ def main(argv=None):
     Log_file.info(args)
     os.makedirs(model_dir, exist_ok=True)
     t0 = time.time()
-    if args.mode in ('recommend', 'similar'):
+    if args.mode in ('recommend', 'similar', 'audience'):
         recommend(args, use_modal, local_rank, Log_file, Log_screen, model_dir, t0)
     else:
         (test if 'test' in args.mode else train)(args, use_modal, local_rank, Log_file, Log_screen, model_dir, t0)

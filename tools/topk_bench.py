@@ -2,7 +2,7 @@
 """Top-K recommendation on one MI355X: a4r_topk_items beside a4r_eval_rank (the same scoring sweep, one rank per user) and beside the torch path a
 user would otherwise write (chunked fp32 matmul, history masked, torch.topk), and recommend() end to end -- one JSON line per configuration.
 
-    python tools/topk_bench.py [--iters N] [--only NAME] [--candidates FRACTION] [--lists C] [--mmr] [--similar] [--bf16]
+    python tools/topk_bench.py [--iters N] [--only NAME] [--candidates FRACTION] [--lists C] [--mmr] [--similar] [--bf16] [--audience]
 
 --bf16 runs the bf16-score leg instead (bf16_cfg): a4r_topk_items_bf16 beside a4r_topk_items / a4r_topk_items_cand of the same build, 32 768 users,
 65 537 items at E = 64 .. 512 and 500 001 items at E = 64 / 128, K = 10 / 100 / 256, the candidate set off and at 0.1, the casts in one leg and outside
@@ -17,6 +17,10 @@ beside the eager composition on the same pools (gather, bmm cosine matrix, a K-r
 --similar runs the similar-items leg instead (similar_cfg): a4r_topk_similar (cosine) for 32 768 query items of a 65 537-row table, K = 10 and 100,
 E = 64 and 128, beside the composition of existing entries (normalised copy + gather + a4r_topk_items with one-id exclusion lists) and beside eager
 torch (normalise, chunked matmul, topk), interleaved rounds after a warm-up.
+--audience runs the audience leg instead (audience_cfg): a4r_topk_users for 4 096 query items over a user table of 262 145 rows, 20 seen ids per user,
+K = 10 and 100, E = 64 and 128, beside the role-swapped a4r_topk_items with empty exclusion lists (the nearest existing launch: it answers another
+question, no user is left out) and beside eager torch (chunked matmul, seen pairs set to -inf, topk), three interleaved rounds after a warm-up (the
+numbers land in profiles/audience_bench.jsonl).
 
 Shapes: 32 768 users x 65 537 items (the evaluation benchmark's shape) and x 500 001 items (the ID tower's 500 000-item table), E = 64, K 10 / 100,
 histories of 20 uniform ids.  Kernel times are HIP-event means over N launches after a warm-up; per-kernel times: run this under
@@ -330,6 +334,69 @@ def bf16_cfg(name, U, N1, E, k, fraction, iters, rounds=3, H=20):
                 identical_lists=round(float((ids == ids_b).all(1).float().mean()), 4), same_id_positions=round(float((ids == ids_b).float().mean()), 4))
 
 
+def eager_audience(item, query, users, seen, k, chunk=512):
+    """what a caller without the kernel writes: the (query, user row) pairs of the seen lists through a lookup of the query items, [chunk, U1]
+    scores, the pad row and the seen pairs set to -inf, torch.topk"""
+    pos = torch.full((item.shape[0],), -1, dtype=torch.long, device=item.device)
+    pos[query.long()] = torch.arange(query.numel(), device=item.device)
+    qp = pos[seen.long().reshape(-1)]
+    row = torch.arange(1, users.shape[0], device=item.device).repeat_interleave(seen.shape[1])
+    qp, row = qp[qp >= 0], row[qp >= 0]
+    rows, scores = [], []
+    for a in range(0, query.numel(), chunk):
+        s = item[query[a:a + chunk].long()] @ users.t()
+        s[:, 0] = -float('inf')
+        m = (qp >= a) & (qp < a + chunk)
+        s[qp[m] - a, row[m]] = -float('inf')
+        v, i = torch.topk(s, k, dim=1)
+        rows.append(i)
+        scores.append(v)
+    return torch.cat(rows), torch.cat(scores)
+
+
+def audience_cfg(name, Q, N1, U1, E, k, iters, rounds=3, H=20):
+    """--audience: a4r_topk_users, the same launch with every seen list empty (what the launch costs without the probes of the lists), the
+    role-swapped a4r_topk_items with empty exclusion lists (the nearest existing launch) and eager torch, interleaved `rounds` times after a warm-up; every round's mean is reported, the ratios from the minima, and the spread of each leg over its
+    rounds."""
+    from adapter4rec_amd import _lib as L
+    g = torch.Generator(device=DEV).manual_seed(5)
+    item = torch.randn(N1, E, device=DEV, generator=g)
+    users = torch.randn(U1, E, device=DEV, generator=g)
+    users[0] = 0
+    query = (torch.randperm(N1 - 1, device=DEV, generator=g)[:Q] + 1).to(torch.int32).contiguous()
+    seen = torch.randint(1, N1, (U1 - 1, H), device=DEV, generator=g, dtype=torch.int32).sort(dim=1).values.contiguous()      # ascending within a row
+    sptr = torch.cat([torch.zeros(1, dtype=torch.int64, device=DEV), torch.arange(U1, device=DEV, dtype=torch.int64) * H]).contiguous()      # row 0 empty
+    flat = seen.reshape(-1)
+    rows = torch.empty(Q, k, dtype=torch.int32, device=DEV)
+    sc = torch.empty(Q, k, dtype=torch.float32, device=DEV)
+    rows_s, sc_s = torch.empty_like(rows), torch.empty_like(sc)
+    prec = item[query.long()].contiguous()
+    ptr0 = torch.zeros(Q + 1, dtype=torch.int32, device=DEV)
+    none = torch.zeros(1, dtype=torch.int32, device=DEV)
+    sptr0 = torch.zeros(U1 + 1, dtype=torch.int64, device=DEV)
+    rows_n, sc_n = torch.empty_like(rows), torch.empty_like(sc)
+    legs = dict(users=lambda: L.topk_users(item, query, users, sptr, flat, None, k, rows, sc),
+                users_empty_lists=lambda: L.topk_users(item, query, users, sptr0, flat, None, k, rows_n, sc_n),      # the two offsets are loaded, no list is probed
+                swapped=lambda: L.topk_items(prec, users, ptr0, none, k, rows_s, sc_s), eager=lambda: eager_audience(item, query, users, seen, k))
+    for fn in legs.values():                                        # warm-up: every leg once before any is timed
+        fn()
+    ms = {n: [] for n in legs}
+    for _ in range(rounds):
+        for n, fn in legs.items():
+            ms[n].append(round(timed(fn, iters if n != 'eager' else max(1, iters // 4)), 4))
+    legs['users']()
+    legs['swapped']()
+    ei, _ = eager_audience(item, query, users, seen, k)
+    torch.cuda.synchronize()
+    spread = {n: round((max(v) - min(v)) / min(v), 4) for n, v in ms.items()}
+    best = min(ms['users'])
+    return dict(name=name, queries=Q, items=N1, user_rows=U1, seen_per_user=H, E=E, k=k, rounds=rounds, iters=iters, **{n + '_ms': v for n, v in ms.items()},
+                spread=spread, users_over_swapped=round(best / min(ms['swapped']), 3),
+                users_empty_lists_over_swapped=round(min(ms['users_empty_lists']) / min(ms['swapped']), 3), eager_over_users=round(min(ms['eager']) / best, 2),
+                queries_per_s=round(Q / best * 1e3), lists_differing_from_swapped=int((rows != rows_s).any(1).sum()),
+                row_agreement_with_eager=round(float((ei.int() == rows).float().mean()), 6))
+
+
 def recommend_cfg(name, U, item_num, k, iters, T=20):
     from adapter4rec_amd.cv import Model
     from adapter4rec_amd.cv.data_utils import get_itemId_embeddings
@@ -364,7 +431,16 @@ def main():
                     help='run the similar-items leg instead: a4r_topk_similar beside the composition of existing entries and eager torch, K = 10 and 100, E = 64 and 128')
     ap.add_argument('--bf16', action='store_true',
                     help='run the bf16-score leg instead: a4r_topk_items_bf16 beside the fp32 entries, K = 10 / 100 / 256, E = 64 .. 512, candidates off and at 0.1')
+    ap.add_argument('--audience', action='store_true',
+                    help='run the audience leg instead: a4r_topk_users beside the role-swapped a4r_topk_items and eager torch, K = 10 and 100, E = 64 and 128')
     a = ap.parse_args()
+    if a.audience:
+        for k in (10, 100):
+            for E in (64, 128):
+                name = f'audience_k{k}_e{E}'
+                if not a.only or a.only == name:
+                    print(json.dumps(audience_cfg(name, 4096, 65537, 262145, E, k, a.iters)), flush=True)
+        return
     if a.bf16:
         for N1, widths, it in ((65537, (64, 128, 256, 512), a.iters), (500001, (64, 128), max(1, a.iters // 4))):
             for E in widths:
