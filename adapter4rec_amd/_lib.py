@@ -987,6 +987,8 @@ SATELLITES = {
     '_lib_score_bf16': ('SCORE_BF16_SIGNATURES', ('eval_rank_bf16', 'topk_items_bf16', 'topk_bf16_ws_bytes')),
     # audience lists, every query item's best users of a user table: include/a4r_audience.h
     '_lib_audience': ('AUDIENCE_SIGNATURES', ('topk_users',)),
+    # top-K with exclusion lists of any length, read from global memory: include/a4r_exclude.h
+    '_lib_exclude': ('EXCLUDE_SIGNATURES', ('topk_items_excl',)),
 }
 
 

@@ -22,6 +22,9 @@
 // Audience lists (a4r_topk_users, include/a4r_audience.h).  audience_partial_kernel is the similar kernel's row set swept over the user table: the
 // K best users of every query item, a user dropped when the item is in the user's own seen list (searched in global memory, no cap on its length).
 //
+// Exclusion lists of any length (a4r_topk_items_excl, include/a4r_exclude.h).  topk_excl_partial_kernel is topk_partial_kernel with the users'
+// lists left in global memory behind int64 offsets, searched the audience kernel's way: no cap on a list's length, no sorting prologue.
+//
 // Where the pieces live.  The key, its decoding, the rank sort of an id list and the search of the sorted list: a4r_select.h, shared with the list
 // kernels.  Here, one copy each for the three partial kernels (fp32, bf16, similar), which keep their own loads and MFMA chains:
 // topk_append (with the trigger protocol), topk_step_end, topk_write_out and topk_compact; on the host topk_args_ok (every export's checks) and
@@ -186,6 +189,70 @@ __global__ void __launch_bounds__(256) topk_partial_kernel(const float* __restri
                 if (!(lo < nex[ul] && excl[ul][lo] == i)) {
                     topk_append(buf, cap, cnt, trig, ul, key, s);
                 }
+            }
+        }
+        __syncthreads();
+        topk_step_end(buf, cap, K, cnt, thr_s, trig, s, kg, thr);
+    }
+    topk_write_out<1>(buf, cap, K, cnt, thr_s, ws, u0, U);
+}
+
+// Exclusion lists of any length (a4r_topk_items_excl, include/a4r_exclude.h): topk_partial_kernel with the users' lists left in global memory.
+// The LDS list, its count and the sorting prologue are gone; the lists come ascending (the caller's contract) behind int64 offsets.  The 16
+// users' two offsets are loaded once into LDS (256 B) -- they do not change with the column, so the sweep loads none -- and a key that beats its
+// threshold is searched in excl_idx[b .. e) by audience_partial_kernel's bisection, behind the cand byte under CAND.  lo <= mid < hi <= e
+// throughout: every read lies inside the user's own list, so an unsorted list can mislist but never strays into a neighbour's.
+template <int E, bool CAND>
+__global__ void __launch_bounds__(256) topk_excl_partial_kernel(const float* __restrict__ prec, const float* __restrict__ item_emb,
+                                                                const int64_t* __restrict__ excl_ptr, const int32_t* __restrict__ excl_idx,
+                                                                uint64_t* __restrict__ ws, int U, int N1, int K, int cap,
+                                                                const uint8_t* __restrict__ cand) {
+    constexpr int KS = E / 16;                       // chunk steps (fp32: 16 k per step)
+    extern __shared__ uint64_t buf[];                // [16][cap] candidate keys
+    __shared__ int64_t xb[16], xe[16];               // the users' lists: excl_idx[xb[ul] .. xe[ul])
+    __shared__ int32_t cnt[16];
+    __shared__ uint64_t thr_s[16];
+    __shared__ int trig;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int r16 = lane & 15, kg = lane >> 4;
+    const int u0 = blockIdx.x * 16;
+    if (tid < 16) {
+        const int u = min(u0 + tid, U - 1);
+        xb[tid] = excl_ptr[u]; xe[tid] = excl_ptr[u + 1];
+        cnt[tid] = 0; thr_s[tid] = 0;
+    }
+    if (tid == 0) trig = -1;
+    uint4 ua[KS];                                    // A operand: the 16 users
+    frag_load<E>(ua, prec, min(u0 + r16, U - 1), kg);
+    __syncthreads();
+    const SweepDeal<> deal(N1, wave);
+    const int nsteps = deal.steps();                 // the 4 waves meet at every step's barrier
+    uint64_t thr[4] = {0, 0, 0, 0};
+    bool live[4];
+#pragma unroll
+    for (int rr = 0; rr < 4; ++rr) live[rr] = u0 + kg * 4 + rr < U;
+    int t = deal.first;
+    uint4 bn[KS];
+    sweep_begin<E, true>(bn, item_emb, deal, r16, kg);
+    for (int s = 0; s < nsteps; ++s, t += deal.tstep) {
+        const int i = 1 + t * 16 + r16;                 // this lane's item column (>= N1 past the end of the table: nothing to add)
+        uint4 b[KS];
+        sweep_next<E, true>(b, bn, item_emb, deal, t, r16, kg);
+        const f32x4_t acc = score_tile<float>(ua, b);
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) {
+            const uint64_t key = topk_key(acc[rr], i);
+            if (i < N1 && live[rr] && key > thr[rr]) {
+                if constexpr (CAND)
+                    if (cand[i] == 0) continue;              // (ahead of the search: under a sparse mask the thresholds stay low for long)
+                const int ul = kg * 4 + rr;
+                const int64_t le = xe[ul];
+                int64_t lo = xb[ul], hi = le;                // lo <= mid < hi <= le throughout: every read lies inside the user's own list
+                while (lo < hi) {
+                    const int64_t mid = lo + ((hi - lo) >> 1);
+                    if (excl_idx[mid] < i) lo = mid + 1; else hi = mid;
+                }
+                if (!(lo < le && excl_idx[lo] == i)) topk_append(buf, cap, cnt, trig, ul, key, s);
             }
         }
         __syncthreads();
@@ -553,6 +620,22 @@ int topk_launch(void* stream, const float* prec, const float* item_emb, const in
     return rc ? rc : topk_finish(s, w, ids, scores, U, K, gy);
 }
 
+// a4r_topk_items_excl's launches: topk_launch's grid, capacity and finish behind the kernel that leaves the lists in global memory
+template <bool CAND>
+int topk_excl_launch(hipStream_t s, const float* prec, const float* item_emb, const int64_t* excl_ptr, const int32_t* excl_idx, const uint8_t* cand,
+                     int32_t* ids, float* scores, uint64_t* w, int U, int N1, int E, int K) {
+    const int gy = topk_ranges(U, N1), cap = topk_cap(K);
+    const dim3 grid((U + 15) / 16, gy);
+    const size_t lds = (size_t)16 * cap * sizeof(uint64_t);
+    int rc = A4R_OK;
+    with_width(WidthsF32{}, E, [&](auto e) {
+        const auto kernel = topk_excl_partial_kernel<decltype(e)::value, CAND>;
+        if ((rc = a4r_set_lds(kernel, lds))) return;
+        hipLaunchKernelGGL(kernel, grid, dim3(256), lds, s, prec, item_emb, excl_ptr, excl_idx, w, U, N1, K, cap, cand);
+    });
+    return rc ? rc : topk_finish(s, w, ids, scores, U, K, gy);
+}
+
 // Row sets of a4r_topk_items_bf16 per (E, K).  LDS bounds them: a row set is a 16-user buffer of 16 cap keys (16 / 32 / 64 KB at K <= 64 / <= 192 / <= 256)
 // beside 17 KB of exclusion ids, so two sets at K <= 64 are 66 KB (two workgroups a CU) and two sets above are one workgroup a CU or none.  Timings
 // choose within that: two sets at E = 128 / 256, where the table's bytes bind; one at E = 64, where the second set's LDS halves
@@ -632,6 +715,17 @@ extern "C" int a4r_topk_users(void* stream, const float* item_emb, const int32_t
     uint64_t* w = static_cast<uint64_t*>(ws);
     return elig ? audience_launch<true>(s, item_emb, query, user_vec, seen_ptr, seen_idx, elig, rows, scores, w, Q, N1, U1, E, K)
                 : audience_launch<false>(s, item_emb, query, user_vec, seen_ptr, seen_idx, nullptr, rows, scores, w, Q, N1, U1, E, K);
+}
+
+extern "C" int a4r_topk_items_excl(void* stream, const float* prec, const float* item_emb, const int64_t* excl_ptr, const int32_t* excl_idx,
+                                   const uint8_t* cand, int32_t* ids, float* scores, void* ws, int U, int N1, int E, int K) {
+    if (!topk_args_ok({prec, item_emb, excl_ptr, excl_idx, ids, scores}, prec, item_emb, ws, U, N1, E, K) ||
+        (reinterpret_cast<uintptr_t>(excl_ptr) & 7u) != 0)
+        return A4R_EINVAL;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    uint64_t* w = static_cast<uint64_t*>(ws);
+    return cand ? topk_excl_launch<true>(s, prec, item_emb, excl_ptr, excl_idx, cand, ids, scores, w, U, N1, E, K)
+                : topk_excl_launch<false>(s, prec, item_emb, excl_ptr, excl_idx, nullptr, ids, scores, w, U, N1, E, K);
 }
 
 extern "C" int a4r_row_inv_norms(void* stream, const float* table, float* inv, int N1, int E) {

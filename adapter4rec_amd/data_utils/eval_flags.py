@@ -1,5 +1,5 @@
 """The flags that restrict or re-rank what evaluation and recommendation range over (--topk .. --eval_negatives_out) and those of --mode similar
-(--similar_*) and --mode audience (--audience_*), for both entry points (run.py, cv/run_adapter.py): their declaration, their refusals, and their
+(--similar_*) and --mode audience (--audience_*) and the exclusion lists of --mode recommend / audience (--exclude_*), for both entry points (run.py, cv/run_adapter.py): their declaration, their refusals, and their
 translation into the arguments of data_utils.metrics (eval_model's restriction, write_recommendations', write_similar_items' and write_audience's
 calls).  No kernel is called from here."""
 import math
@@ -9,9 +9,12 @@ import torch.distributed as dist
 
 from .._lib_diversify import MMR_MAX_POOL
 from .._lib_user_lists import LIST_MAX
-from .metrics import (SCORE_DTYPES, SIMILAR_METRICS, Diversify, EvalNegatives, candidate_mask, item_counts, read_candidate_lists, read_candidates,
-                      read_audience_users, read_similar_items, write_audience, write_eval_negatives, write_recommendations, write_similar_items)
+from .metrics import (SCORE_DTYPES, SIMILAR_METRICS, Diversify, EvalNegatives, candidate_mask, item_counts, merge_exclude_lists, read_candidate_lists,
+                      read_candidates, read_audience_users, read_exclude_lists, read_full_histories, read_similar_items, write_audience,
+                      write_eval_negatives, write_recommendations, write_similar_items)
 from .preprocess import read_behavior_names
+
+EXCLUDE_HISTORIES = ('window', 'full')       # --exclude_history: the reader's window of a user's line (the exclusion as it was), or the whole line
 
 
 def add_eval_flags(p):
@@ -34,6 +37,8 @@ def add_eval_flags(p):
     p.add_argument('--audience_items', type=str, default=None)         # --mode audience: a file of item names, one per line -- the query items, in file order (default: every item)
     p.add_argument('--audience_users', type=str, default=None)         # --mode audience: a file of user names, one per line -- the eligible users (default: every user)
     p.add_argument('--score_dtype', type=str, default='fp32', choices=list(SCORE_DTYPES))      # --mode test / recommend and the per-epoch evaluation: bf16 = score against the item table on the bf16 MFMA (operands rounded, fp32 sums)
+    p.add_argument('--exclude_lists', type=str, default=None)          # --mode recommend / audience: a file of `user_name \t item_name item_name ...` lines -- items never recommended to the user, of any number
+    p.add_argument('--exclude_history', type=str, default='window', choices=list(EXCLUDE_HISTORIES))      # --mode recommend / audience: full = exclude every item of the user's whole line of the behaviours file, not only the last max_seq_len + 3
 
 
 def check_flags(args):
@@ -44,6 +49,47 @@ def check_flags(args):
     check_similar_flag(args)
     check_audience_flag(args)
     check_score_dtype_flag(args)
+    check_exclude_flag(args)                 # (last: every message above keeps its precedence)
+
+
+def check_exclude_flag(args):
+    """--exclude_lists FILE and --exclude_history full are honoured by --mode recommend and --mode audience, alone, together (their union is
+    excluded) and beside --candidate_items and --diversify mmr; under any other mode, beside --candidate_lists (a shortlist is filtered where it
+    is made) and beside --score_dtype bf16 (a4r_topk_items_excl scores in fp32 only) they are refused instead of ignored."""
+    given = []
+    if getattr(args, 'exclude_lists', None):
+        given.append('--exclude_lists')
+    if getattr(args, 'exclude_history', 'window') != 'window':
+        given.append(f'--exclude_history {args.exclude_history}')
+    for flag in given:
+        if args.mode not in ('recommend', 'audience'):
+            raise ValueError(f'{flag} is honoured by --mode recommend and --mode audience only, not by --mode {args.mode}')
+        if getattr(args, 'candidate_lists', None):
+            raise ValueError(f'{flag} and --candidate_lists cannot be combined: a shortlist is filtered where it is made')
+        if getattr(args, 'score_dtype', 'fp32') != 'fp32':
+            raise ValueError(f'{flag} and --score_dtype {args.score_dtype} cannot be combined: a4r_topk_items_excl scores in fp32 only')
+
+
+def exclude_lists_from_args(args, behaviors_path, name2id, user_names, item_names, Log_file):
+    """--exclude_lists FILE / --exclude_history full -> the ``exclude_lists`` keyword of write_recommendations / write_audience: {} without
+    either flag (the calls are then the ones made before), else the union of the file's lists and the users' whole lines of the behaviours
+    file, and one log line."""
+    lists, sources, bad_users, bad_items = None, [], 0, 0
+    if getattr(args, 'exclude_history', 'window') == 'full':
+        lists, bu, bi = read_full_histories(behaviors_path, name2id, user_names, item_names)
+        sources.append(f'{behaviors_path} (--exclude_history full)')
+        bad_users, bad_items = bad_users + bu, bad_items + bi
+    if getattr(args, 'exclude_lists', None):
+        more, bu, bi = read_exclude_lists(args.exclude_lists, user_names, item_names)
+        lists = merge_exclude_lists(lists, more)
+        sources.append(args.exclude_lists)
+        bad_users, bad_items = bad_users + bu, bad_items + bi
+    if lists is None:
+        return {}
+    lens = [len(set(v)) for v in lists.values()]
+    Log_file.info(f'exclude lists: {len(lists)} users, {sum(lens)} ids in all, longest {max(lens, default=0)}; {bad_users} user names and {bad_items} item names '
+                  f'unknown, skipped <- {" + ".join(sources)}')
+    return dict(exclude_lists=lists)
 
 
 def check_score_dtype_flag(args):
@@ -216,8 +262,8 @@ def recommend_out_path(args, model_dir):
 
 def write_recommend_mode(args, model, users_test, hist_test, item_embeddings, batch_size, behaviors_path, name2id, model_dir, Log_file):
     """The tail of --mode recommend in both entry points: the --topk next items after every user's whole known sequence of the test split, within
-    --candidate_items / --candidate_lists and re-ranked under --diversify mmr, written by rank 0 to --recommend_out under the names of the
-    behaviours file."""
+    --candidate_items / --candidate_lists and re-ranked under --diversify mmr, without the items of --exclude_lists / --exclude_history full,
+    written by rank 0 to --recommend_out under the names of the behaviours file."""
     user_names, item_names = read_behavior_names(behaviors_path, name2id, args.max_seq_len, args.min_seq_len)
     mask, lists = _candidates_from_args(args, user_names, item_names, Log_file)
     spec = None
@@ -226,7 +272,8 @@ def write_recommend_mode(args, model, users_test, hist_test, item_embeddings, ba
         Log_file.info(f'diversify: mmr, lambda {spec.lam:g}, pool {spec.pool}')
     out = write_recommendations(model, users_test, hist_test, item_embeddings, args.topk, batch_size, args, user_names, item_names,
                                 recommend_out_path(args, model_dir), candidates=mask, candidate_lists=lists, diversify=spec, Log_file=Log_file,
-                                **score_dtype_from_args(args, Log_file))
+                                **score_dtype_from_args(args, Log_file),
+                                **exclude_lists_from_args(args, behaviors_path, name2id, user_names, item_names, Log_file))
     if out:
         Log_file.info(f'recommend: top-{args.topk} lists of {len(users_test)} users -> {out}')
 
@@ -266,4 +313,5 @@ def write_audience_mode(args, model, users_test, hist_test, item_embeddings, bat
         eligible = read_audience_users(args.audience_users, user_names)
         Log_file.info(f'audience users: {int(eligible.sum())} of {len(user_names)} from {args.audience_users}')
     write_audience(model, users_test, hist_test, item_embeddings, args.topk, batch_size, args, user_names, item_names,
-                   audience_out_path(args, model_dir), item_ids=query, eligible=eligible, Log_file=Log_file)
+                   audience_out_path(args, model_dir), item_ids=query, eligible=eligible, Log_file=Log_file,
+                   **exclude_lists_from_args(args, behaviors_path, name2id, user_names, item_names, Log_file))

@@ -589,8 +589,112 @@ def _recommend_inputs(user_seqs, exclude, uids, T):
     return ids, mask, ptr, flat
 
 
+def _id_array(x):
+    """any iterable of item ids (a list, an array, a tensor, a set) -> int64 array [n]"""
+    if isinstance(x, torch.Tensor):
+        x = x.cpu().numpy()
+    elif not isinstance(x, np.ndarray):
+        x = list(x)
+    return np.asarray(x, dtype=np.int64).reshape(-1)
+
+
+def exclude_union_csr(base, exclude_lists, uids, n1):
+    """The listed users' exclusion lists as a4r_topk_items_excl reads them: for each u of ``uids``, the union of ``base[u]`` and
+    ``exclude_lists[u]`` (a user without an entry adds nothing), the ids outside 1 .. n1 - 1 dropped, ascending, each once -> (ptr int64 [n + 1],
+    flat int32 ids + one spare 0), built on the host.  There is no cap on a list's length."""
+    rows = []
+    for u in uids:
+        u = int(u)
+        more = exclude_lists.get(u)
+        x = _id_array(base[u])
+        if more is not None:
+            x = np.concatenate([x, _id_array(more)])
+        rows.append(np.unique(x[(x >= 1) & (x < n1)]))
+    ptr, flat, _ = _csr_int32(rows)
+    return ptr, flat
+
+
+def _exclude_lists_checked(exclude_lists, candidate_lists, score_dtype):
+    """``exclude_lists`` beside what it cannot be combined with: refused, not ignored, before anything is encoded"""
+    if exclude_lists is None:
+        return
+    if not hasattr(exclude_lists, 'get'):
+        raise ValueError(f'exclude_lists: a dict {{uid: item ids}} expected, got {type(exclude_lists).__name__}')
+    if candidate_lists is not None:
+        raise ValueError('exclude_lists cannot be combined with candidate_lists: a shortlist is filtered where it is made')
+    if score_dtype == 'bf16':
+        raise ValueError("exclude_lists cannot be combined with score_dtype 'bf16': a4r_topk_items_excl scores in fp32 only")
+
+
+def read_exclude_lists(path, user_names, item_names):
+    """An exclusion-list file -> ({uid: [item ids]}, n_unknown_users, n_unknown_items): read_candidate_lists' line format, ``user_name \\t
+    item_name item_name ...``; blank lines are ignored, a user named twice has the lines appended, a user named without items has an empty
+    list.  Unlike a candidate list, a name that is no user or no item of this dataset is skipped and counted (distinct names), not raised: a
+    block list and a user's old interactions legitimately name items that are no longer in the catalogue, and those cannot be recommended
+    anyway."""
+    users = {name: u for u, name in enumerate(user_names) if name is not None}
+    items = {name: i for i, name in enumerate(item_names) if i > 0 and name is not None}
+    out, bad_users, bad_items = {}, set(), set()
+    with open(path) as f:
+        for line in f:
+            if not line.strip():
+                continue
+            head, _, rest = line.rstrip('\n').partition('\t')
+            u = users.get(head.strip())
+            if u is None:
+                bad_users.add(head.strip())
+                continue
+            ids = out.setdefault(u, [])
+            for name in rest.split():
+                i = items.get(name)
+                if i is None:
+                    bad_items.add(name)
+                else:
+                    ids.append(i)
+    return out, len(bad_users), len(bad_items)
+
+
+def read_full_histories(behaviors_path, name2id, user_names, item_names):
+    """The behaviours file itself as exclusion lists -> read_exclude_lists' triple: every item of a kept user's whole line (``user_name \\t
+    item_name item_name ...``), not only the last max_seq_len + 3 that read_behaviors keeps.  ``name2id``: the item file's names (a name outside
+    it is no item at all and is skipped uncounted, as read_behaviors skips it); a name of the item file that the reader dropped from the
+    catalogue, and a user it dropped, are skipped and counted."""
+    users = {name: u for u, name in enumerate(user_names) if name is not None}
+    items = {name: i for i, name in enumerate(item_names) if i > 0 and name is not None}
+    out, bad_users, bad_items = {}, set(), set()
+    with open(behaviors_path) as f:
+        for line in f:
+            parts = line.strip('\n').split('\t')
+            if len(parts) < 2 or not parts[0].strip():
+                continue
+            u = users.get(parts[0].strip())
+            if u is None:
+                bad_users.add(parts[0].strip())
+                continue
+            ids = out.setdefault(u, [])
+            for name in parts[1].split():
+                i = items.get(name)
+                if i is not None:
+                    ids.append(i)
+                elif name in name2id:
+                    bad_items.add(name)
+    return out, len(bad_users), len(bad_items)
+
+
+def merge_exclude_lists(*lists):
+    """{uid: ids} dicts (None = none) -> one dict with each user's lists appended, or None when every one is None"""
+    given = [x for x in lists if x is not None]
+    if not given:
+        return None
+    out = {}
+    for d in given:
+        for u, ids in d.items():
+            out.setdefault(u, []).extend(int(i) for i in ids)
+    return out
+
+
 def recommend(model, user_seqs, item_embeddings, k, args, exclude=None, user_ids=None, candidates=None, candidate_lists=None, diversify=None,
-              score_dtype='fp32'):
+              score_dtype='fp32', exclude_lists=None):
     """The k best items for each listed user (default: every user of ``user_seqs``), after the user's sequence.
 
     ``user_seqs[u]``: the user's item ids (1 .. N); its last ``max_seq_len`` items go through ``user_encoder``, left-padded as an evaluation
@@ -608,15 +712,24 @@ def recommend(model, user_seqs, item_embeddings, k, args, exclude=None, user_ids
     scores, in pick order: they need not descend.
     ``score_dtype`` 'bf16': the scores come from the bf16 MFMA at the rounded operands (a4r_topk_items_bf16, include/a4r_score_bf16.h: the bits
     eval_ranks(score_dtype='bf16') compares) -- the table is cast once per call, each batch's user vectors once; the returned scores are those
-    fp32 sums.  Honoured with and without ``candidates``; refused beside ``candidate_lists`` and ``diversify``, whose kernels score in fp32 only."""
-    return _recommend(model, user_seqs, item_embeddings, k, args, exclude, user_ids, candidates, candidate_lists, diversify, False, score_dtype)[:2]
+    fp32 sums.  Honoured with and without ``candidates``; refused beside ``candidate_lists`` and ``diversify``, whose kernels score in fp32 only.
+    ``exclude_lists`` ({uid: an iterable of item ids}, of any length; a user without an entry adds nothing): each user's list is added to what the
+    user excludes already (``exclude[u]``, or ``user_seqs[u]``); the union goes sorted, each id once and without the ids outside 1 .. N, to
+    a4r_topk_items_excl (include/a4r_exclude.h), which searches it in global memory -- every batch of the call goes through that entry, under
+    ``candidates`` with its mask, and the 264-id cap does not apply (to ``exclude`` neither, then).  ``diversify`` composes: its pool is that
+    entry's output.  Refused beside ``candidate_lists`` (a shortlist is filtered where it is made) and ``score_dtype`` 'bf16' (the entry scores in
+    fp32 only).  None: nothing changes."""
+    return _recommend(model, user_seqs, item_embeddings, k, args, exclude, user_ids, candidates, candidate_lists, diversify, False, score_dtype,
+                      exclude_lists)[:2]
 
 
-def _recommend(model, user_seqs, item_embeddings, k, args, exclude, user_ids, candidates, candidate_lists, diversify, want_ild, score_dtype='fp32'):
+def _recommend(model, user_seqs, item_embeddings, k, args, exclude, user_ids, candidates, candidate_lists, diversify, want_ild, score_dtype='fp32',
+               exclude_lists=None):
     """recommend's body -> (ids, scores, ild): ild None unless ``want_ild`` under ``diversify``, then fp32 [U, 2] = the intra-list diversity (mean
     1 - cosine over a list's pairs of items) of the plain top-k list and of the re-ranked one, both from the one pool."""
     _both_refused(candidates, candidate_lists)
     bf16 = _score_dtype_checked(score_dtype, candidate_lists=candidate_lists, diversify=diversify) == 'bf16'
+    _exclude_lists_checked(exclude_lists, candidate_lists, score_dtype)
     if diversify is not None and not 1 <= int(k) <= diversify.pool:
         raise ValueError(f'diversify: k = {int(k)} outside 1 .. pool = {diversify.pool}')
     inner = _inner(model, args)
@@ -631,7 +744,12 @@ def _recommend(model, user_seqs, item_embeddings, k, args, exclude, user_ids, ca
         return (torch.zeros(0, k, dtype=torch.long, device=dev), torch.zeros(0, k, dtype=torch.float32, device=dev),
                 torch.zeros(0, 2, dtype=torch.float32, device=dev) if want_ild else None)
     kk = k if diversify is None else diversify.pool                # what the top-K entry is asked for
-    ids_np, mask_np, ptr_np, flat_np = _recommend_inputs(user_seqs, exclude, uids, T)
+    if exclude_lists is None:
+        ids_np, mask_np, ptr_np, flat_np = _recommend_inputs(user_seqs, exclude, uids, T)
+    else:                                                          # the union as an int64-offset CSR, of any length: a4r_topk_items_excl's
+        ids_np, mask_np = _user_inputs(user_seqs, uids, T)
+        ptr_np, flat_np = exclude_union_csr(user_seqs if exclude is None else exclude, exclude_lists, uids, emb.shape[0])
+        xptr = torch.from_numpy(ptr_np).to(dev)                    # uploaded once per call, sliced per batch
     step = int(os.environ.get('A4R_EVAL_USER_BATCH', 0)) or 8192          # (eval_ranks' user batch)
     flat = torch.from_numpy(flat_np).to(dev)
     emb_b = _cast_bf16(emb) if bf16 else None                     # the scoring copy; the fp32 table stays: the user tower reads it
@@ -646,10 +764,12 @@ def _recommend(model, user_seqs, item_embeddings, k, args, exclude, user_ids, ca
             nb = b - a
             prec = _encode_users(inner, emb, ids_np, mask_np, a, b)
             h0, h1 = int(ptr_np[a]), int(ptr_np[b])
-            ptr = torch.from_numpy((ptr_np[a:b + 1] - h0).astype(np.int32)).to(dev)
+            ptr = torch.from_numpy((ptr_np[a:b + 1] - h0).astype(np.int32)).to(dev) if exclude_lists is None else None
             ids = torch.empty(nb, kk, dtype=torch.int32, device=dev)
             scores = torch.empty(nb, kk, dtype=torch.float32, device=dev)
-            if bf16:
+            if exclude_lists is not None:                             # (the batch's offsets count from the whole array's start: a slice, no copy)
+                L.topk_items_excl(prec, emb, xptr[a:b + 1], flat, cand, kk, ids, scores)
+            elif bf16:
                 L.topk_items_bf16(_cast_bf16(prec), emb_b, ptr, flat[h0:h1 + 1], kk, ids, scores, cand)
             elif candidate_lists is not None:
                 l0, l1 = int(lptr[a]), int(lptr[b])
@@ -675,7 +795,7 @@ def _recommend(model, user_seqs, item_embeddings, k, args, exclude, user_ids, ca
 
 
 def write_recommendations(model, user_seqs, user_history, item_embeddings, k, batch_size, args, user_names, item_names, path, candidates=None,
-                          candidate_lists=None, diversify=None, Log_file=None, score_dtype='fp32'):
+                          candidate_lists=None, diversify=None, Log_file=None, score_dtype='fp32', exclude_lists=None):
     """The runners' --mode recommend: the k next items after every user's whole known sequence (``user_seqs[u]``, the evaluation input of the
     test split, whose last item is the held-out one), excluding ``user_history[u]`` plus that last item -- everything the user is known to have
     seen.  Users are sharded over the data-parallel ranks as eval_model shards them; rank 0 writes ``path``: one line per user, in uid order,
@@ -684,7 +804,7 @@ def write_recommendations(model, user_seqs, user_history, item_embeddings, k, ba
     ``diversify``: as recommend's.  The file's format is unchanged; a line's scores are the items' relevance scores in the order the items were
     picked, no longer necessarily descending.  ``Log_file`` then gets one line, ``recommend_ild``: the mean intra-list diversity (mean 1 - cosine
     over a list's pairs of items) of the plain top-k lists and of the re-ranked ones, over the users with at least two items (``k of n users``).
-    ``score_dtype``: as recommend's."""
+    ``score_dtype``: as recommend's.  ``exclude_lists``: as recommend's -- added to the exclusion above, of any length."""
     n_users = len(user_seqs)
     world, rank_id, uids = _shard_users(n_users, batch_size)
     exclude = {}
@@ -692,7 +812,8 @@ def write_recommendations(model, user_seqs, user_history, item_embeddings, k, ba
         u = int(u)
         if u not in exclude:
             exclude[u] = np.concatenate([np.asarray(user_history[u], dtype=np.int64).reshape(-1), np.asarray(user_seqs[u][-1:], dtype=np.int64)])
-    ids, scores, ild = _recommend(model, user_seqs, item_embeddings, k, args, exclude, uids, candidates, candidate_lists, diversify, True, score_dtype)
+    ids, scores, ild = _recommend(model, user_seqs, item_embeddings, k, args, exclude, uids, candidates, candidate_lists, diversify, True, score_dtype,
+                                  exclude_lists)
     ids, scores = _gather_cat(ids, world), _gather_cat(scores, world)
     if ild is not None:                                            # gathered over the ranks the way the ids are
         ild = _gather_cat(ild, world)
@@ -933,12 +1054,12 @@ def audience(model, user_seqs, item_embeddings, k, args, item_ids=None, seen=Non
 
 
 def write_audience(model, user_seqs, user_history, item_embeddings, k, batch_size, args, user_names, item_names, path, item_ids=None, eligible=None,
-                   Log_file=None):
+                   Log_file=None, exclude_lists=None):
     """The runners' --mode audience: the k best users of the query items ``item_ids`` (default: every item 1 .. N) among ``eligible`` (bool
     [n_users], default: every user), a user never listed for an item of ``user_history[u]`` or the last item of ``user_seqs[u]`` -- everything
     the user is known to have seen: write_recommendations' exclusion, without its 264-id cap.  The users are sharded over the data-parallel
     ranks for the user tower and their vectors gathered as get_item_embeddings gathers its shards; the query items are sharded as
-    write_similar_items shards them.  Rank 0 writes ``path``: one line per query item that has at least one user, in query order,
+    write_similar_items shards them.  ``exclude_lists`` ({uid: item ids}, of any length): merged into the seen lists.  Rank 0 writes ``path``: one line per query item that has at least one user, in query order,
     ``item_name \\t user_1 ... user_k \\t score_1 ... score_k`` (pad slots omitted, scores as %.9g).  ``Log_file`` gets one line, ``audience``.
     Returns the path on rank 0, None elsewhere."""
     k = int(k)
@@ -955,6 +1076,8 @@ def write_audience(model, user_seqs, user_history, item_embeddings, k, batch_siz
     lo, hi, chunk, world = _my_shard(n_users)
     table = _user_table(_gather_shards(user_vectors(model, user_seqs, emb, args, np.arange(lo, hi, dtype=np.int64)), n_users, chunk, world))
     seen = [np.concatenate([np.asarray(user_history[u], dtype=np.int64).reshape(-1), np.asarray(user_seqs[u][-1:], dtype=np.int64)]) for u in range(n_users)]
+    if exclude_lists is not None:
+        seen = [np.concatenate([x, _id_array(exclude_lists[u])]) if exclude_lists.get(u) is not None else x for u, x in enumerate(seen)]
     ptr, flat = audience_seen_csr(seen, n_users)
     world, rank_id, rows = _shard_users(nq, batch_size)
     ids, scores = _audience(table, emb, k, q[np.asarray(rows, dtype=np.int64)], torch.from_numpy(ptr).to(dev), torch.from_numpy(flat).to(dev), elig)

@@ -547,6 +547,7 @@ int a4r_score_ce_bwd_items(void* stream, const float* prec, const float* table, 
 #include "a4r_similar.h"
 #include "a4r_score_bf16.h"
 #include "a4r_audience.h"
+#include "a4r_exclude.h"
 
 /* The learned item-ID table of the IDRec baseline (ABI 410; Downstream/CV/model/model.py: nn.Embedding(item_num + 1, E, padding_idx=0), fed the flat
  * slot ids of a batch).  a4r_id_index, once per step: rows[i] = ids[i] when 0 <= ids[i] <= item_num, else 0 and counted in *err (overwritten: the

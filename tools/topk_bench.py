@@ -2,7 +2,12 @@
 """Top-K recommendation on one MI355X: a4r_topk_items beside a4r_eval_rank (the same scoring sweep, one rank per user) and beside the torch path a
 user would otherwise write (chunked fp32 matmul, history masked, torch.topk), and recommend() end to end -- one JSON line per configuration.
 
-    python tools/topk_bench.py [--iters N] [--only NAME] [--candidates FRACTION] [--lists C] [--mmr] [--similar] [--bf16] [--audience]
+    python tools/topk_bench.py [--iters N] [--only NAME] [--candidates FRACTION] [--lists C] [--mmr] [--similar] [--bf16] [--audience] [--exclude]
+
+--exclude runs the exclusion-list leg instead (exclude_cfg): a4r_topk_items_excl for 32 768 users of a 65 537-row table, K = 10 and 100, E = 64 and
+128, (a) beside a4r_topk_items of the same build on identical lists of 20 and of 264 ids, (b) at 1 000 and 5 000 ids per user -- drawn uniformly, and
+the user's own best items -- beside eager torch (chunked matmul, listed pairs set to -inf, topk), three interleaved rounds after a warm-up (the
+numbers land in profiles/exclude_bench.jsonl).
 
 --bf16 runs the bf16-score leg instead (bf16_cfg): a4r_topk_items_bf16 beside a4r_topk_items / a4r_topk_items_cand of the same build, 32 768 users,
 65 537 items at E = 64 .. 512 and 500 001 items at E = 64 / 128, K = 10 / 100 / 256, the candidate set off and at 0.1, the casts in one leg and outside
@@ -397,6 +402,80 @@ def audience_cfg(name, Q, N1, U1, E, k, iters, rounds=3, H=20):
                 row_agreement_with_eager=round(float((ei.int() == rows).float().mean()), 6))
 
 
+def eager_exclude(prec, emb, lists, k, chunk=2048):
+    """what a caller without the kernel writes for lists of any length: [chunk, N1] scores, the pad row and the listed pairs set to -inf, topk"""
+    ids, scores = [], []
+    for a in range(0, prec.shape[0], chunk):
+        s = prec[a:a + chunk] @ emb.t()
+        s[:, 0] = -float('inf')
+        s.scatter_(1, lists[a:a + chunk].long(), -float('inf'))
+        v, i = torch.topk(s, k, dim=1)
+        ids.append(i)
+        scores.append(v)
+    return torch.cat(ids), torch.cat(scores)
+
+
+def own_best(prec, emb, n, chunk=2048):
+    """every user's n highest-scoring items, ascending by id: the hard case of an exclusion list -- exactly the keys that beat the threshold"""
+    out = []
+    for a in range(0, prec.shape[0], chunk):
+        s = prec[a:a + chunk] @ emb.t()
+        s[:, 0] = -float('inf')
+        out.append(torch.topk(s, n, dim=1).indices.to(torch.int32).sort(dim=1).values)
+    return torch.cat(out).contiguous()
+
+
+def exclude_cfg(name, U, N1, E, k, iters, rounds=3):
+    """--exclude: (a) a4r_topk_items_excl beside a4r_topk_items of the same build on identical lists of 20 and of 264 ids (both entries serve
+    them); (b) a4r_topk_items_excl at 1 000 and 5 000 ids per user beside eager torch, the lists drawn uniformly and as the user's own best items.
+    All legs interleaved `rounds` times after a warm-up of each; every round's mean is reported, the ratios from the minima, and the spread of each
+    leg over its rounds."""
+    from adapter4rec_amd import _lib as L
+    g = torch.Generator(device=DEV).manual_seed(7)
+    emb = torch.randn(N1, E, device=DEV, generator=g)
+    prec = torch.randn(U, E, device=DEV, generator=g)
+    ids = torch.empty(U, k, dtype=torch.int32, device=DEV)
+    sc = torch.empty(U, k, dtype=torch.float32, device=DEV)
+    ids_x, sc_x = torch.empty_like(ids), torch.empty_like(sc)
+    legs, eager, checks = {}, set(), {}
+    for H in (20, 264):
+        lists = torch.randint(1, N1, (U, H), device=DEV, generator=g, dtype=torch.int32).sort(dim=1).values.contiguous()      # ascending within a user
+        p32 = (torch.arange(U + 1, device=DEV, dtype=torch.int32) * H).contiguous()
+        p64 = p32.long().contiguous()
+        flat = lists.reshape(-1)
+        legs[f'items_h{H}'] = (lambda p=p32, f=flat: L.topk_items(prec, emb, p, f, k, ids, sc))
+        legs[f'excl_h{H}'] = (lambda p=p64, f=flat: L.topk_items_excl(prec, emb, p, f, None, k, ids_x, sc_x))
+        checks[f'h{H}'] = (f'items_h{H}', f'excl_h{H}')
+    for H in (1000, 5000):
+        for draw in ('uniform', 'top'):
+            lists = (torch.randint(1, N1, (U, H), device=DEV, generator=g, dtype=torch.int32).sort(dim=1).values.contiguous() if draw == 'uniform'
+                     else own_best(prec, emb, H))
+            p64 = (torch.arange(U + 1, device=DEV, dtype=torch.int64) * H).contiguous()
+            legs[f'excl_{draw}{H}'] = (lambda p=p64, f=lists.reshape(-1): L.topk_items_excl(prec, emb, p, f, None, k, ids_x, sc_x))
+            legs[f'eager_{draw}{H}'] = (lambda l=lists: eager_exclude(prec, emb, l, k))
+            eager.add(f'eager_{draw}{H}')
+            checks[f'{draw}{H}'] = (f'eager_{draw}{H}', f'excl_{draw}{H}')
+    for fn in legs.values():                                        # warm-up: every leg once before any is timed
+        fn()
+    ms = {n: [] for n in legs}
+    for _ in range(rounds):
+        for n, fn in legs.items():
+            ms[n].append(round(timed(fn, max(1, iters // 4) if n in eager else iters), 4))
+    agree = {}
+    for what, (ref, new) in checks.items():                         # equal lists on the lists both entries serve; up to near-ties against eager
+        r = legs[ref]()
+        legs[new]()
+        torch.cuda.synchronize()
+        agree[what] = round(float((r[0].int() == ids_x).float().mean()), 6)
+    best = {n: min(v) for n, v in ms.items()}
+    spread = {n: round((max(v) - min(v)) / min(v), 4) for n, v in ms.items()}
+    ratios = {f'excl_over_items_h{H}': round(best[f'excl_h{H}'] / best[f'items_h{H}'], 3) for H in (20, 264)}
+    ratios.update({f'eager_over_excl_{d}{H}': round(best[f'eager_{d}{H}'] / best[f'excl_{d}{H}'], 2) for H in (1000, 5000) for d in ('uniform', 'top')})
+    ratios.update({f'excl_{d}{H}_over_excl_h20': round(best[f'excl_{d}{H}'] / best['excl_h20'], 3) for H in (1000, 5000) for d in ('uniform', 'top')})
+    return dict(bench='topk', name=name, box=torch.cuda.get_device_name(0), users=U, items=N1, E=E, k=k, rounds=rounds, iters=iters,
+                **{n + '_ms': v for n, v in ms.items()}, spread=spread, **ratios, id_agreement=agree)
+
+
 def recommend_cfg(name, U, item_num, k, iters, T=20):
     from adapter4rec_amd.cv import Model
     from adapter4rec_amd.cv.data_utils import get_itemId_embeddings
@@ -433,7 +512,16 @@ def main():
                     help='run the bf16-score leg instead: a4r_topk_items_bf16 beside the fp32 entries, K = 10 / 100 / 256, E = 64 .. 512, candidates off and at 0.1')
     ap.add_argument('--audience', action='store_true',
                     help='run the audience leg instead: a4r_topk_users beside the role-swapped a4r_topk_items and eager torch, K = 10 and 100, E = 64 and 128')
+    ap.add_argument('--exclude', action='store_true',
+                    help='run the exclusion-list leg instead: a4r_topk_items_excl beside a4r_topk_items (20 / 264 ids) and eager torch (1 000 / 5 000 ids), K = 10 and 100, E = 64 and 128')
     a = ap.parse_args()
+    if a.exclude:
+        for k in (10, 100):
+            for E in (64, 128):
+                name = f'exclude_k{k}_e{E}'
+                if not a.only or a.only == name:
+                    print(json.dumps(exclude_cfg(name, 32768, 65537, E, k, a.iters)), flush=True)
+        return
     if a.audience:
         for k in (10, 100):
             for E in (64, 128):
